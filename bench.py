@@ -21,7 +21,7 @@ across column shards, it is the reference's two passes (A^T r, then A D).
           products and the failure flag); several feature blocks -> columns (the
           reference's P-way split, cpu_calculation.py:23-27: two passes over A per
           iteration and one all-reduce of m + 2 + N fp64 on the residual side).
-          Beside it, from the same run: "weak" (BASELINE configs[2]'s shape,
+          Beside it, with --full, from the same run: "weak" (BASELINE configs[2]'s shape,
           m=8192 n=65536*N -- n = 524288 at N = 8 -- every GPU holding the 2 GiB of
           N = 1; unit block-iters/s = N x global iterations/s, with its own
           speedup_vs_n1), "columns" (the reference's column split of the same
@@ -34,25 +34,41 @@ across column shards, it is the reference's two passes (A^T r, then A D).
   --config 3 / 4: configs[3] (1048576 x 4096 fp32) / configs[4] (k = 128
           right-hand sides on bf16 A), one GPU.
 
-Timing (every workload): W untimed warm-up iterations; an eager window of
-max(K, 512) iterations (side legs: max(K, 128)) with HIP events around every kernel
-on the solver stream (the per-kernel averages behind `roofline`, and the clock ramp
-of a fresh box), lengthened on a one-pass leg until it contains an exact-gradient
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the value line
+needs: set-up, W untimed warm-up iterations, a calibration window of 512 (--ramp)
+eager iterations (below), one untimed replay of every graph size the window uses
+(at most 127 iterations), ONE timed window of exactly K graph-replayed iterations,
+the outputs if --dump-outputs DIR is given, and the JSON line.  Everything else the
+benchmark measures rides behind --full: the CPU baselines, the vendor GEMV
+yardsticks, the N = 1 side legs, the other legs of an N > 1 run, and the median
+over five windows.
+
+Timing (every workload): W untimed warm-up iterations; an eager calibration window of
+512 iterations (--full: max(K, 512); side legs: max(K, 128)) with HIP events around
+every kernel on the solver stream (the cost of the exact-gradient refresh that the
+rate folds in, the per-kernel averages behind `roofline`, and the clock ramp of a
+fresh box), lengthened on a one-pass leg until it contains an exact-gradient
 refresh (a one-pass leg that timed none fails);
-then `--windows` (default 5) windows of exactly K graph-replayed iterations, each
-bracketed by a barrier and device synchronisation, max over ranks.  value and
-ms_per_step come from the median window, with the one-pass exact-gradient refresh
+then `--windows` (default 1; --full: 5) windows of exactly K graph-replayed iterations,
+each bracketed by a barrier and device synchronisation, max over ranks.  value and
+ms_per_step come from the (median) window, with the one-pass exact-gradient refresh
 (one A^T r pass every 256 iterations) folded in at its amortised rate: a window's
 time minus the refreshes it happened to contain, plus K/256 refreshes, each at the
 event-timed refresh cost.
 
-N = 1 side legs (the same JSON line, each with its own ms_per_step, roofline and
-kernel averages; a leg that fails records {"error": ...}): "config3" (configs[3],
+--dump-outputs DIR: after the last timed window, what the timed path computed is
+written as DIR/x.npy (the iterate a caller of the solver receives: fp64 (n,); the
+panel path: fp32 (n, k)); with several ranks DIR/x_rank<r>.npy per rank.  The
+inputs are seeded (--seed), so the same arguments give the same problem and the
+same number of iterations before the dump in every run and every build.
+
+--full, N = 1 side legs (the same JSON line, each with its own ms_per_step, roofline
+and kernel averages; a leg that fails records {"error": ...}): "config3" (configs[3],
 1048576 x 4096 fp32), "config4" (configs[4], k = 128 right-hand sides on bf16 A,
 the MFMA panel path) and "config2_one_gpu" (configs[2]'s whole 8192 x 524288
 matrix on this one GPU).  --no-side-legs skips them.
 
-Launch: python bench.py [--gpus N --steps K --warmup W].  For N > 1 under
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR].  For N > 1 under
 torch.distributed.run (one process per GPU, RANK/LOCAL_RANK/WORLD_SIZE env) the
 ranks run directly; without it (WORLD_SIZE unset) this process touches no GPU,
 starts `python -m torch.distributed.run --nproc-per-node N bench.py <same args>`
@@ -109,14 +125,20 @@ def parse():
                          "2 = 8192x524288 fp32 split over the N GPUs (strong), 3 = 1048576x4096 fp32, "
                          "4 = k=128 right-hand sides on bf16 A")
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=256,
-                    help="iterations per timed window (default 256)")
-    ap.add_argument("--warmup", type=int, default=200,
-                    help="untimed iterations before the windows (default 200)")
+    ap.add_argument("--steps", type=int, default=None,
+                    help="iterations per timed window (default 256; --config 3: 30)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the value line: CPU baselines, vendor GEMV yardsticks, the N = 1 side "
+                         "legs, the other legs of an N > 1 run, and the median over 5 windows (default: a plain "
+                         "run -- set-up, warm-up, one window of --steps iterations, the JSON line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what they computed (the iterate x) as DIR/<name>.npy")
+    ap.add_argument("--warmup", type=int, default=None,
+                    help="untimed iterations before the windows (default 200; --config 3: 40)")
     ap.add_argument("--ramp", type=int, default=512,
                     help="minimum length of the eager window with per-kernel events (default 512 iterations)")
-    ap.add_argument("--windows", type=int, default=5,
-                    help="timed windows of exactly --steps iterations; value uses the median (default 5)")
+    ap.add_argument("--windows", type=int, default=None,
+                    help="timed windows of exactly --steps iterations; value uses the median (default 1; --full: 5)")
     ap.add_argument("--m", type=int, default=M)
     ap.add_argument("--n-per-gpu", type=int, default=N_PER_GPU)
     ap.add_argument("--block", type=int, default=1)
@@ -184,12 +206,20 @@ def parse():
         a.n_per_gpu = 524288 // world
     elif a.config == 3:
         a.m, a.n_per_gpu = 1048576, 4096
-        a.steps, a.warmup = min(a.steps, 30), min(a.warmup, 40)   # 2.7 ms per iteration
+        # 2.7 ms per iteration: shorter defaults; --steps / --warmup given on the command line hold
+        a.steps = 30 if a.steps is None else a.steps
+        a.warmup = 40 if a.warmup is None else a.warmup
     elif a.config == 4:
         a.rhs = 128
     if a.shard == "auto":
         a.shard = "rows" if a.block == 1 else "columns"
-    a.windows = max(1, a.windows)
+    a.steps = 256 if a.steps is None else a.steps
+    a.warmup = 200 if a.warmup is None else a.warmup
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be positive and --warmup non-negative")
+    a.windows = max(1, (5 if a.full else 1) if a.windows is None else a.windows)
+    if not a.full:     # a plain run: the value line alone
+        a.no_cpu = a.no_side_legs = a.no_strong = True
     return a
 
 
@@ -341,9 +371,15 @@ def eager_window_len(steps, ramp, warmup, period, onepass):
     return n
 
 
+def primer_len(steps, graph):
+    """untimed iterations before the single window of a plain run: one replay of every graph the
+    window uses (graphs of `graph` iterations and the remainder), at most 2 graph - 1"""
+    return steps if steps < graph else graph + steps % graph
+
+
 def measure(ctx, args, m, n_total):
-    """W warm-up iterations, an eager window with per-kernel HIP events (max(K, 512) iterations),
-    then `windows` graph windows of exactly K iterations (see the module docstring).  A window is
+    """W warm-up iterations, an eager window with per-kernel HIP events (512 iterations; --full:
+    max(K, 512)), then `windows` graph windows of exactly K iterations (see the module docstring).  A window is
     valid when it ran the iteration the solve started with (one pass or two) and lost no
     iterations; if a one-pass launch failed before the windows (every window then runs on the
     two-pass kernels), the solver is reset and the whole sequence measured once more."""
@@ -376,7 +412,8 @@ def measure(ctx, args, m, n_total):
         sync()
         # eager window: kernel averages (events on the solver stream) + clock ramp, and on a
         # one-pass leg at least one exact-gradient refresh
-        n_ev = eager_window_len(args.steps, args.ramp, args.warmup, gc.solver_stat("refresh_period"), op0)
+        n_ev = eager_window_len(args.steps if args.full else 0, args.ramp, args.warmup,
+                                gc.solver_stat("refresh_period"), op0)
         progress(f"  eager window of {n_ev} iterations with kernel events")
         gc.set_kernel_timing(True)
         r0 = gc.solver_stat("refreshes")
@@ -397,6 +434,13 @@ def measure(ctx, args, m, n_total):
         # failed one-pass launch lost -- such a window did not do its K iterations, and a window
         # after a fallback runs the two-pass kernels: neither counts toward the median
         wins = []
+        # a plain run has one window and no median to drop a first replay from: every graph size the
+        # window will replay (64s and the binary remainder of K) is replayed once, untimed, before it
+        n_prime = 0 if args.full else primer_len(args.steps, args.graph_max if args.graph_max > 0 else 64)
+        if n_prime:
+            gc.solver_step(n_prime)
+            sync()
+            gc.solver_status()
         progress(f"  {args.windows} graph windows of {args.steps} iterations")
         for _ in range(args.windows):
             r0 = gc.solver_stat("refreshes")
@@ -414,7 +458,7 @@ def measure(ctx, args, m, n_total):
         if attempt == 1:
             raise MeasureError("every timed window lost one-pass iterations or fell back to two passes "
                                "(another process holds CUs?)")
-    assert st["iters"] == args.warmup + n_ev + args.windows * args.steps or st["stopped"], st
+    assert st["iters"] == args.warmup + n_ev + n_prime + args.windows * args.steps or st["stopped"], st
     return dict(gc=gc, windows=wins, el_events=el_ev, n_events=n_ev, kernel_ms=times, samples=samples, status=st,
                 refresh_ms=refresh_ms, refresh_period=period, w_local=gc.MAT_WIDTH, m_local=gc.MAT_HEIGHT,
                 b=b, mu=mu, fallbacks=gc.solver_stat("fallbacks"), onepass=gc.solver_stat("onepass"),
@@ -672,6 +716,23 @@ def panel_fill_bytes(m, w, k, which, d_split=2, r_pieces=2):
     return 2 * m * w + (m // 256) * d_split * 2 * k * w
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """DIR/<name>.npy for every array (fp32 stays fp32, everything else fp64), at most 64 MB in all:
+    an array above its share of the cap is written as a fixed (seeded) sample of its elements."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_CAP_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+        if a.nbytes > share:
+            idx = np.sort(np.random.RandomState(20190325).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def main_panel(args):
     emit(measure_panel(args))
 
@@ -723,13 +784,20 @@ def measure_panel(args):
     pl.solver_reset(B, mu, use_graph=True)
     pl.solver_step(args.warmup)
     sync()
-    n_ev = max(args.steps, args.ramp)          # eager window: kernel averages + clock ramp
+    n_ev = max(args.steps, args.ramp) if args.full else args.ramp   # eager window: kernel averages + clock ramp
     pl.set_kernel_timing(True)
     el_ev = timed_window(ctx, sync, pl.solver_step, n_ev)
     kms, samples = pl.kernel_times()
     pl.set_kernel_timing(False)
+    n_prime = 0 if args.full else primer_len(args.steps, 8)   # as measure(): the panel graph holds 8 iterations
+    if n_prime:
+        pl.solver_step(n_prime)
+        sync()
     wins = [timed_window(ctx, sync, pl.solver_step, args.steps) for _ in range(args.windows)]
     st = pl.solver_status()
+    if args.dump_outputs:
+        sync()
+        dump_outputs(args.dump_outputs, {"x": pl.solver_x_device().t().cpu().numpy()})   # (n, k) fp32
     el_graph = median(wins)
     w = pl.MAT_WIDTH
     dom = max(("pass1_mfma", "pass2_mfma"), key=lambda q: kms[q])
@@ -773,7 +841,7 @@ def measure_panel(args):
             # the rate depends on the iterate: early in a solve x changes in every column and pass 1
             # stores all of X; later it skips the tiles the step left alone (pass 2 measured 201 µs at
             # iterations 5-517, 184 µs at 1500-2012)
-            "windows_from_iteration": args.warmup + n_ev,
+            "windows_from_iteration": args.warmup + n_ev + n_prime,
             "kernel_avg_ms": kms, "status": st,
         },
         "roofline": {
@@ -881,7 +949,7 @@ def single_leg(ctx, args, m, n, label, steps_cap=None, ramp_cap=None):
 def panel_leg(args):
     """configs[4] through measure_panel, summarised for the N = 1 line"""
     a2 = argparse.Namespace(**vars(args))
-    a2.config, a2.rhs, a2.m, a2.n_per_gpu = 4, 128, M, N_PER_GPU
+    a2.config, a2.rhs, a2.m, a2.n_per_gpu, a2.dump_outputs = 4, 128, M, N_PER_GPU, None
     # windows of whole 8-iteration graph replays, at least 64 iterations: a 20-iteration window ran
     # 4 of its iterations as eager launches (the panel graph holds 8), 5 % below the replayed rate
     a2.steps = max(64, -(-a2.steps // 8) * 8)
@@ -992,6 +1060,10 @@ def main():
     m = args.m
     n_total, scaling = main_shape(args, G)
     res = measure(ctx, args, m, n_total)
+    if args.dump_outputs:
+        # the iterate as the last timed step left it (measure() ends on the collective status call)
+        x = res["gc"].solver_x(complete=False)
+        dump_outputs(args.dump_outputs, {"x" if G == 1 else f"x_rank{ctx.rank}": x})
     w, ml = res["w_local"], res["m_local"]
     rows = res["gc"].shard == "rows"
     K = args.steps
@@ -1178,7 +1250,7 @@ def main():
                 o["config"] = f"m={m} n={args.n_per_gpu} on rank 0's GPU alone (no communicator), same run"
                 out["n1_same_run"] = o
                 speedups(out, n1, G)
-    if G == 1 and args.type == "float" and res is not None:
+    if G == 1 and args.full and args.type == "float" and res is not None:
         out["config"]["vendor_gemv_yardstick"] = vendor_yardstick(res["gc"])
         out["config"]["vendor_iteration_yardstick"] = vendor_iteration_yardstick(res["gc"], res["b"], res["mu"])
     if G == 1 and side_legs_apply(args):

@@ -290,9 +290,52 @@ def test_launch_decision():
 
 def test_side_legs_ride_on_the_default_line_only():
     b = _bench()
-    assert b.side_legs_apply(_parse(b, []))
+    assert b.side_legs_apply(_parse(b, ["--full"]))
+    assert not b.side_legs_apply(_parse(b, []))          # a plain run: the value line alone
     for argv in (["--no-side-legs"], ["--config", "3"], ["--type", "bf16"], ["--block", "2"], ["--comm"]):
-        assert not b.side_legs_apply(_parse(b, argv)), argv
+        assert not b.side_legs_apply(_parse(b, ["--full"] + argv)), argv
+
+
+def test_plain_run_is_the_value_line_alone():
+    """without --full: one window of exactly --steps iterations, no CPU baseline, no side legs, no
+    other N > 1 legs; --full keeps the five-window median and every leg; --steps / --warmup given on
+    the command line hold for every configuration"""
+    b = _bench()
+    a = _parse(b, ["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert (a.full, a.steps, a.warmup, a.windows) == (False, 20, 5, 1)
+    assert a.no_cpu and a.no_side_legs and a.no_strong and a.dump_outputs is None
+    a = _parse(b, ["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert (a.full, a.steps, a.warmup, a.windows) == (True, 20, 5, 5)
+    assert not (a.no_cpu or a.no_side_legs or a.no_strong)
+    assert _parse(b, ["--windows", "3"]).windows == 3 and _parse(b, ["--full", "--windows", "3"]).windows == 3
+    a = _parse(b, ["--config", "3"])
+    assert (a.steps, a.warmup) == (30, 40)
+    a = _parse(b, ["--config", "3", "--steps", "100", "--warmup", "64"])
+    assert (a.steps, a.warmup) == (100, 64)
+    a = _parse(b, [])
+    assert (a.steps, a.warmup) == (256, 200)
+    # the calibration window of a plain run does not grow with --steps
+    assert b.eager_window_len(0, 512, 5, 256, 1) == 512 and b.eager_window_len(0, 512, 5, 256, 0) == 512
+    # ... and the untimed replay of the window's graph sizes is bounded
+    assert [b.primer_len(k, 64) for k in (1, 20, 63, 64, 65, 256, 2000)] == [1, 20, 63, 64, 65, 64, 80]
+    assert all(b.primer_len(k, 8) <= 15 for k in range(1, 300))
+
+
+def test_dump_outputs_writes_float_arrays_within_the_cap(tmp_path):
+    import numpy as np
+    b = _bench()
+    x = np.arange(1000, dtype=np.float64) / 7
+    y = np.arange(12, dtype=np.float32).reshape(3, 4).T          # not contiguous
+    b.dump_outputs(str(tmp_path / "out"), {"x": x, "y": y})
+    gx, gy = np.load(tmp_path / "out" / "x.npy"), np.load(tmp_path / "out" / "y.npy")
+    assert gx.dtype == np.float64 and np.array_equal(gx, x)
+    assert gy.dtype == np.float32 and np.array_equal(gy, y)
+    # above the cap: the same seeded sample every time
+    b.DUMP_CAP_BYTES = 800
+    b.dump_outputs(str(tmp_path / "a"), {"x": x})
+    b.dump_outputs(str(tmp_path / "b"), {"x": x})
+    sa, sb = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "b" / "x.npy")
+    assert sa.nbytes <= 800 and sa.size == 100 and np.array_equal(sa, sb) and np.isin(sa, x).all()
 
 
 def test_one_pass_eager_window_always_times_a_refresh():

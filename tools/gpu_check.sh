@@ -7,7 +7,7 @@ shift
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_20_5.json 2> $OUT/bench_20_5.err &&
-timeout -k 10 300 python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err &&
+timeout -k 10 300 python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err &&
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 &&
 timeout -k 10 1500 python3 -u -m pytest tests -m gpu -x -v --timeout 900 --timeout-method thread "$@" > $OUT/pytest.log 2>&1
 rc=$?

@@ -18,7 +18,7 @@ for K in 128 64; do
       python3 $R/bench.py --rhs $K --steps 4 --warmup 2 --ramp 4 --windows 1 --no-cpu > $OUT/b_k$K.json 2> $OUT/k$K.err || exit 1
 done
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- \
-    python3 $R/bench.py --config 4 --steps 100 --warmup 100 --no-cpu > $OUT/bench_trace.json 2> $OUT/trace.err || exit 1
+    python3 $R/bench.py --full --config 4 --steps 100 --warmup 100 --no-cpu > $OUT/bench_trace.json 2> $OUT/trace.err || exit 1
 cd $R
 python3 tools/pmc_summary.py $OUT/k128 > $OUT/summary_k128.txt
 python3 tools/pmc_summary.py $OUT/k64 > $OUT/summary_k64.txt

@@ -11,7 +11,7 @@ OUT=$R/${1:-gpurun_out/prof}
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-B="python3 $R/bench.py"
+B="python3 $R/bench.py --full"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_driver -- \
     $B --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/trace_driver.err || exit $?
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_c1 -- \

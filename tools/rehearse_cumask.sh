@@ -10,5 +10,5 @@ N=${1:-2}; shift
 OUT=gpurun_out/rehearse_cumask
 mkdir -p $OUT
 BPGL_BENCH_DEVICE=0 BPGL_BENCH_CU_PARTITION=1 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 \
-    --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29700 + N)) bench.py --gpus $N "$@" \
+    --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29700 + N)) bench.py --gpus $N --full "$@" \
     > $OUT/n$N.json 2> $OUT/n$N.err
