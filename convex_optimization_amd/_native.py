@@ -63,6 +63,8 @@ _SIGS = {
                                   ctypes.POINTER(_f64), ctypes.POINTER(_f64)]),
     "bpgl_solver_stat": (_int, [_p, ctypes.c_char_p, ctypes.POINTER(_i64)]),
     "bpgl_solver_residual": (_p, [_p]),
+    "bpgl_solver_gap": (_int, [_p, _p, _p, ctypes.POINTER(_f64)]),
+    "bpgl_gather_columns": (_int, [_p, _p, _i64, _p, _i64]),
     "bpgl_iterate": (_int, [_p, _i64, _p, _f64, _p, _p, _p, _p, _f64, ctypes.POINTER(_i64)]),
     "bpgl_set_kernel_timing": (_int, [_p, _int]),
     "bpgl_set_tuning": (_int, [_p, ctypes.c_char_p, _i64]),

@@ -14,6 +14,9 @@ path (``gpu_calculation``) never calls them.
   fun_diag_ATA        cpu_calculation.py:35-42  per-block column sums of squares
   fun_s22             cpu_calculation.py:45-46  A_p s21
   fun_dd_p            cpu_calculation.py:49-50  (w, 1) -> (P, w/P, 1)
+
+New beside them (no counterpart in the reference): ``duality_gap`` and ``gap_safe_keep``, the
+numpy fp64 restatement of the device's optimality certificate and screening rule.
 """
 import numpy as np
 
@@ -59,3 +62,43 @@ def fun_s22(A_bp, s21):
 
 def fun_dd_p(P, descent_d):
     return np.reshape(descent_d, (P, -1, 1))
+
+
+# ---------------------------------------------------------------------------
+# New beside the reference's eight: the duality-gap certificate and the gap-safe
+# screening rule, the host restatement of bpgl_solver_gap.
+# ---------------------------------------------------------------------------
+def _gap_terms(A, b, x, mu):
+    A = np.asarray(A, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64).reshape(-1)
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    mu = float(mu)
+    r = A @ x - b
+    g = A.T @ r
+    rr = float(r @ r)
+    primal = 0.5 * rr + mu * float(np.abs(x).sum())
+    gn = float(np.max(np.abs(g)))                  # NaN propagates
+    scale = min(1.0, mu / gn) if gn > 0.0 else 1.0   # theta = scale r is dual feasible
+    dual = -0.5 * scale * scale * rr - scale * float(r @ b)
+    out = dict(primal=primal, dual=dual, gap=primal - dual, scale=scale, gnorm_inf=gn)
+    return A, g, out
+
+
+def duality_gap(A, b, x, mu):
+    """dict(primal, dual, gap, scale, gnorm_inf) of 1/2 ||A x - b||^2 + mu ||x||_1 at x.
+
+    With r = A x - b and g = A^T r: scale = min(1, mu / ||g||_inf) (1 when g = 0), the dual
+    point scale r, dual = -1/2 scale^2 ||r||^2 - scale r.b and gap = primal - dual >= P(x) - P*."""
+    return _gap_terms(A, b, x, mu)[2]
+
+
+def gap_safe_keep(A, b, x, mu, return_score=False):
+    """bool (K,): False where the gap-safe rule proves x*_j = 0.
+
+    score_j = scale |g_j| + ||a_j|| sqrt(2 max(gap, 0)); column j is kept iff not (score_j < mu),
+    so a NaN keeps everything.  ``return_score``: also return the scores."""
+    A, g, t = _gap_terms(A, b, x, mu)
+    radius = np.sqrt(2.0 * np.maximum(t["gap"], 0.0))
+    score = t["scale"] * np.abs(g) + np.sqrt(np.square(A).sum(axis=0)) * radius
+    keep = ~(score < float(mu))
+    return (keep, score) if return_score else keep

@@ -21,6 +21,7 @@
 #include "bpgl_host.h"
 #include "bpgl_kernels.h"
 #include "bpgl_onepass.h"
+#include "bpgl_gap.h"
 
 using namespace bpgl;
 
@@ -60,6 +61,8 @@ struct bpgl_ctx {
     int64_t lda = 0, block_stride = 0;
     bool bound = false, have_diag = false;
     Params p{};
+    double* gap_buf = nullptr;   // scratch of bpgl_solver_gap: partials, then the result
+    int* gap_counts = nullptr;
     // multi-GPU
     ncclComm_t comm = nullptr;
     int rank = 0, nranks = 1;
@@ -201,7 +204,8 @@ int op_rows_eff(const bpgl_ctx* c) {
 
 // scratch layout (offsets in bytes)
 struct Layout {
-    int64_t slab_g, slab_s, D, parts, parts2, comm, r, Ax, st, diag, rec, opG, opUs, opPG, opS, opABE, total;
+    int64_t slab_g, slab_s, D, parts, parts2, comm, r, Ax, st, diag, rec, opG, opUs, opPG, opS, opABE, gap, gapcnt,
+        total;
 };
 Layout layout(const bpgl_ctx* c) {
     Carve k;
@@ -224,6 +228,9 @@ Layout layout(const bpgl_ctx* c) {
     L.opPG = k.take(op ? 8 * c->m * c->op_SB : 0);
     L.opS = k.take(op && c->rows ? 8 * c->m : 0);
     L.opABE = k.take(op && c->rows ? 8 * 4 : 0);
+    // bpgl_solver_gap (bpgl_gap.h): [kGapBlocks][4] partials + the result, and the screen's per-block counts
+    L.gap = k.take(8 * (4 * kGapBlocks + kGapRes));
+    L.gapcnt = k.take(4 * cdiv((int64_t)c->nblock * c->wp, kThreads));
     L.total = k.off;
     return L;
 }
@@ -707,7 +714,7 @@ int recover_onepass(bpgl_ctx* c, DevState& st) {
 extern "C" {
 
 const char* bpgl_last_error(void) { return bpgl_host::g_err.c_str(); }
-int bpgl_version(void) { return 302; }
+int bpgl_version(void) { return 303; }
 
 int bpgl_stream_create(int device, const uint32_t* cu_mask, int32_t mask_words, void** out) {
     if (!out) return fail(BPGL_E_ARG, "out is null");
@@ -856,6 +863,8 @@ int bpgl_bind(bpgl_ctx* c, const void* A, int64_t lda, int64_t block_stride, voi
     p.diag = (const double*)(s + L.diag);
     p.rec = (const double*)(s + L.rec);
     p.wall_tick_s = c->wall_tick_s;
+    c->gap_buf = (double*)(s + L.gap);
+    c->gap_counts = (int*)(s + L.gapcnt);
     c->op = OnePassArgs{};
     if (c->op_shape) {
         c->op.G = (double*)(s + L.opG);
@@ -1142,6 +1151,76 @@ int bpgl_solver_stat(bpgl_ctx* c, const char* key, int64_t* value) {
 }
 
 const double* bpgl_solver_residual(bpgl_ctx* c) { return c ? c->p.r : nullptr; }
+
+int bpgl_solver_gap(bpgl_ctx* c, double* g_all, uint8_t* keep, double* out6) {
+    int rc;
+    if ((rc = check_ready(c))) return rc;
+    if (c->comm || c->external || c->nranks != 1 || c->rows)
+        return fail(BPGL_E_STATE, "bpgl_solver_gap serves single-rank contexts only (no RCCL communicator, "
+                                  "bpgl_set_ranks or row shards)");
+    if (!c->have_diag) return fail(BPGL_E_STATE, "bpgl_diag_ata must run before bpgl_solver_gap");
+    if (!c->solver) return fail(BPGL_E_STATE, "bpgl_solver_reset has not been called");
+    if (!g_all || !out6) return fail(BPGL_E_ARG, "g_all and out6 must be non-null");
+    HIP_TRY(hipSetDevice(c->device));
+    {   // as bpgl_solver_status: wait, and re-run iterations a failed one-pass launch lost
+        DevState st;
+        if ((rc = read_state(c, st))) return rc;
+        if (st.op_fail && (rc = recover_onepass(c, st))) return rc;
+    }
+    // exact g = A_b^T r for every block, through the split-K slab (free between iterations) into the
+    // caller's buffer: the carried gradient op.G and every other piece of solver state stay untouched
+    const int64_t n = (int64_t)c->nblock * c->wp;
+    for (int b = 0; b < c->nblock; ++b) {
+        if ((rc = colpass(c, 0, c->p.r, c->p.slab_g, b))) return rc;
+        hipLaunchKernelGGL(k_colreduce, dim3((unsigned)cdiv(c->wp, kThreads)), dim3(kThreads), 0, c->stream,
+                           c->p.slab_g, c->wp, c->nchunk, g_all + (int64_t)b * c->wp, (double*)nullptr);
+        LAUNCH_CHECK("k_colreduce");
+    }
+    const int nparts = (int)std::min<int64_t>(cdiv(std::max<int64_t>(c->m, n), kThreads), kGapBlocks);
+    double* res = c->gap_buf + 4 * kGapBlocks;
+    hipLaunchKernelGGL(k_gap_partials, dim3((unsigned)nparts), dim3(kThreads), 0, c->stream, c->p, g_all, c->gap_buf);
+    LAUNCH_CHECK("k_gap_partials");
+    hipLaunchKernelGGL(k_gap_final, dim3(1), dim3(kThreads), 0, c->stream, c->gap_buf, nparts, c->p.mu, res);
+    LAUNCH_CHECK("k_gap_final");
+    if (keep) {
+        const int64_t nb = cdiv(n, kThreads);
+        hipLaunchKernelGGL(k_gap_screen, dim3((unsigned)nb), dim3(kThreads), 0, c->stream, c->p, g_all, res, keep,
+                           c->gap_counts);
+        LAUNCH_CHECK("k_gap_screen");
+        hipLaunchKernelGGL(k_gap_count, dim3(1), dim3(kThreads), 0, c->stream, c->gap_counts, (long long)nb, res);
+        LAUNCH_CHECK("k_gap_count");
+    }
+    HIP_TRY(hipMemcpyAsync(out6, res, 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (!keep) out6[5] = (double)((int64_t)c->nblock * c->w);
+    return 0;
+}
+
+int bpgl_gather_columns(bpgl_ctx* c, const int32_t* cols, int64_t n_out, void* A_out, int64_t lda_out) {
+    int rc;
+    if ((rc = check_ready(c))) return rc;
+    if (!cols || !A_out) return fail(BPGL_E_ARG, "cols and A_out must be non-null");
+    const int V = vec_elems(c->dtype);
+    if (n_out <= 0) return fail(BPGL_E_ARG, "n_out must be > 0");
+    if (lda_out < n_out || lda_out % V)
+        return fail(BPGL_E_ARG, "lda_out (%lld) must be >= n_out (%lld) and a multiple of %d", (long long)lda_out,
+                    (long long)n_out, V);
+    if (((uintptr_t)A_out) % 16) return fail(BPGL_E_ARG, "A_out must be 16-byte aligned");
+    if (lda_out / V > (int64_t)0x7fffffff * kThreads) return fail(BPGL_E_ARG, "lda_out too large");
+    HIP_TRY(hipSetDevice(c->device));
+    GatherArgs a{c->A, c->lda, c->block_stride, c->w, (int64_t)c->nblock * c->w, c->m, cols, n_out, A_out, lda_out};
+    const int64_t gx = cdiv(lda_out / V, kThreads);
+    // about 4096 blocks; each thread walks rows blockIdx.y, + gridDim.y, ... with its column offsets in registers
+    const int64_t gy = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(c->m, 65535), cdiv(4096, gx)));
+    const dim3 g((unsigned)gx, (unsigned)gy), b(kThreads);
+    switch (c->dtype) {
+        case BPGL_F32: hipLaunchKernelGGL(k_gather_cols<4>, g, b, 0, c->stream, a); break;
+        case BPGL_F64: hipLaunchKernelGGL(k_gather_cols<8>, g, b, 0, c->stream, a); break;
+        default: hipLaunchKernelGGL(k_gather_cols<2>, g, b, 0, c->stream, a); break;
+    }
+    LAUNCH_CHECK("k_gather_cols");
+    return 0;
+}
 
 int bpgl_iterate(bpgl_ctx* c, int64_t n_iter, const int32_t* order, double mu, const double* b, double* x,
                  double* err_iter, double* time_iter, double err_bound, int64_t* iters_done) {

@@ -28,6 +28,10 @@ g += gamma U and the next shrink), with an exact g = A^T r every 256
 iterations; with several blocks (or ``onepass`` = 0) it is the two-pass
 sequence colpass / shrink / rowpass / rowreduce (+ line search) / update.
 
+Also new: ``duality_gap`` -- the duality-gap certificate of the current
+point and the gap-safe screening mask -- and ``gather_columns``, the column gather that
+``lasso.ClassLassoScreened`` uses to continue on the columns not yet proved zero.
+
 Every compute call goes through libbpgl.so (``_native``); there is no
 alternative path.  Multi-GPU: pass ``comm=`` (see ``distributed.RankComm``);
 A is then this rank's column shard of every feature block (``shard="columns"``,
@@ -338,6 +342,48 @@ class GPU_Calculation:
         if self._err_iter is None:
             return None, None
         return self._err_iter.cpu().numpy().copy(), self._time_iter.cpu().numpy().copy()
+
+    # -- optimality certificate, gap-safe screening, column gather --
+    def duality_gap(self, screen=True):
+        """Duality gap of the solver's current point (include/bpgl.h bpgl_solver_gap): a dict of
+        ``primal, dual, gap, scale, gnorm_inf, n_keep`` (P(x) - P* <= gap) plus ``g_all``, the
+        exact A^T r as a device (Block, W) fp64 view.  With ``screen`` also ``keep``, a device
+        bool (Block, W): False where the gap-safe rule proves the optimum's coefficient is 0.
+        Single-rank contexts only, after ``solver_reset``; read-only for the solve."""
+        B, W, Wp = self.Block, self.MAT_WIDTH, self.MAT_WIDTH_PAD
+        out = (ctypes.c_double * 6)()
+        with self._on_stream():
+            g = torch.empty((B, Wp), dtype=torch.float64, device=self.device)
+            keep = torch.empty((B, Wp), dtype=torch.uint8, device=self.device) if screen else None
+            N.check(N.lib().bpgl_solver_gap(self._ctx, N.ptr(g), N.ptr(keep), out), "bpgl_solver_gap")
+            res = dict(primal=out[0], dual=out[1], gap=out[2], scale=out[3], gnorm_inf=out[4],
+                       n_keep=int(out[5]), g_all=g[:, :W])
+            self._gap_keep = keep          # the raw (Block, W_pad) bytes, padding included
+            if screen:
+                res["keep"] = keep[:, :W].bool()
+        return res
+
+    def gather_columns(self, cols):
+        """New device tensor (H, n_out) in the storage dtype with column c = column ``cols[c]`` of A
+        (global index b W + j; -1 gives a zero column); ``cols``: a host or device integer
+        sequence in any order.  Contiguous when n_out is a multiple of 16 bytes' worth of
+        elements -- a new ``GPU_Calculation`` then binds it in place -- else a view of a padded
+        buffer (include/bpgl.h bpgl_gather_columns)."""
+        V = N.VEC_ELEMS[self._dt]
+        # allocated on the caller's stream (which _on_stream orders around the library's), so the
+        # caching allocator reuses the block across contexts, each of which has a stream of its own
+        if isinstance(cols, torch.Tensor):
+            ct = cols.reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
+        else:
+            ct = torch.from_numpy(np.ascontiguousarray(np.asarray(cols).reshape(-1), dtype=np.int32)).to(
+                self.device)
+        n_out = int(ct.numel())
+        lda_out = -(-max(n_out, 1) // V) * V
+        out = torch.empty((self.MAT_HEIGHT, lda_out), dtype=N.TORCH_DTYPE[self._dt], device=self.device)
+        with self._on_stream():
+            N.check(N.lib().bpgl_gather_columns(self._ctx, N.ptr(ct), n_out, N.ptr(out), lda_out),
+                    "bpgl_gather_columns")
+        return out if lda_out == n_out else out[:, :n_out]
 
     # -- caller-performed exchange (validation of the sharded kernels on one GPU) --
     def set_ranks(self, rank, nranks):

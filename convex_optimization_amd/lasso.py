@@ -13,6 +13,8 @@ Reference drivers (lasso.py:25-613) and what stands in for each here:
   ClassLassoCB_v2 (lasso.py:357-613)  "pure GPU" loop -> ClassLassoDevice: every
                   step on the device, one hipGraph replay per iteration, no
                   host round trip until the end.
+  (none)                              ClassLassoScreened: the device loop with a
+                  duality-gap stopping rule and gap-safe column screening (new).
   ClassLassoCPU   (lasso.py:25-169)   not provided: the reference's Pool-based
                   CPU path stays the reference's (tests/ and bench.py time its
                   restatement in oracle/ as the CPU baseline).
@@ -212,6 +214,118 @@ class ClassLassoDevice(_Driver):
         self.x = gc.solver_x(complete=False).reshape(-1, 1)
         self.iters = st["iters"]
         self.stopped = st["stopped"]
+        return t_elapsed
+
+
+class ClassLassoScreened(_Driver):
+    """Device loop with a duality-gap stopping rule and gap-safe column screening (new: the
+    reference has neither).
+
+    ``run(GAP_BOUND=None, SILENCE=False)`` runs ``check_every`` block updates at a time on the
+    device (the loop of ``ClassLassoDevice``: cyclic order, x0 = 0), then takes
+    ``GPU_Calculation.duality_gap`` and appends dict(t, gap, primal, n_active) to ``self.trace``.
+    It stops when ``GAP_BOUND`` is a float and gap <= GAP_BOUND * 1/2 ||b||^2, or after
+    ``ITER_MAX`` block updates in total.  When the columns the screening rule keeps, rounded up
+    to a multiple of q = BLOCK * 16, are at most ``shrink`` times the active ones, the kept
+    columns (ascending original index, padded to that multiple with the highest-score screened
+    columns: keeping a few provably-zero columns is harmless, and every storage type then binds
+    in place) are gathered into a narrower matrix, a new ``GPU_Calculation`` of the same class
+    (and ``TYPE``) and the same BLOCK is built over it and the solve continues there from
+    x0 = x[kept].  The original context stays alive.
+
+    After ``run``: ``x`` (K, 1) with zeros outside ``active`` (the original indices still
+    active), ``certificate`` (one ``duality_gap`` of that x on the FULL A, taken on the original
+    context), ``iters``, ``stopped``, ``trace``, ``gather_seconds`` (the gathers alone) and ``compact_seconds``
+    (gather, the new context, its diag, reset and graph capture).
+
+      * A gap computed on a compacted problem is a valid bound on P(x) - P*: the dropped
+        columns are zero at the optimum, so the optimum (and P*) is unchanged.  Its dual point
+        need not be feasible for the dropped columns, hence the final full-A certificate.
+      * After the first compaction the feature blocks are re-formed (BLOCK equal slices of the
+        kept columns), so the trajectory deliberately departs from the reference's; it is still
+        an exact-line-search descent to the same optimum.
+      * ``shrink=0`` disables compaction: the run is then ``ClassLassoDevice``'s, bit for bit
+        (``duality_gap`` is read-only for the solve).
+    """
+    descript = "MI355X screened loop"
+
+    def __init__(self, gpu_cal, d_ATA, A, b, mu, BLOCK, ITER_MAX, check_every=64, shrink=0.75, use_graph=True):
+        _Driver.__init__(self, gpu_cal, d_ATA, A, b, mu, BLOCK, ITER_MAX)
+        if int(check_every) <= 0:
+            raise ValueError("check_every must be > 0")
+        if not 0.0 <= float(shrink) < 1.0:
+            raise ValueError("shrink must lie in [0, 1)")
+        self.check_every = int(check_every)
+        self.shrink = float(shrink)
+        self.use_graph = use_graph
+
+    def _compact(self, cur, res, active, n_new):
+        """The narrower context over the kept columns (+ padding), its x0 and its original indices."""
+        import torch
+        keep = res["keep"].reshape(-1)
+        kept = torch.nonzero(keep).reshape(-1)
+        pad = n_new - int(kept.numel())
+        if pad > 0:
+            radius = (2.0 * max(res["gap"], 0.0)) ** 0.5
+            score = res["scale"] * res["g_all"].reshape(-1).abs() \
+                + cur._diag[:, :cur.MAT_WIDTH].reshape(-1).sqrt() * radius
+            score = torch.where(keep, torch.full_like(score, -float("inf")), score)
+            kept = torch.cat([kept, torch.topk(score, pad).indices])
+        sel = torch.sort(kept).values
+        t0 = time.time()
+        At = cur.gather_columns(sel)
+        cur.stream.synchronize()
+        self.gather_seconds += time.time() - t0
+        cur.solver_status()
+        x0 = cur.solver_x_device().reshape(-1)[sel].clone()
+        nxt = type(self.gpu_cal)(At, self.BLOCK, device=cur.device)
+        return nxt, x0, active[sel.cpu().numpy()]
+
+    def run(self, GAP_BOUND=None, SILENCE=False):
+        bounded = isinstance(GAP_BOUND, float)
+        K = self.A_SHAPE[1]
+        q = self.BLOCK * 16
+        target = GAP_BOUND * 0.5 * float(np.square(self.b).sum()) if bounded else None
+        screen = self.shrink > 0.0
+        cur = self.gpu_cal
+        active = np.arange(K, dtype=np.int64)
+        self.trace = []
+        self.gather_seconds = self.compact_seconds = 0.0
+        stopped = False
+        t = 0
+        start = time.time()
+        cur.solver_reset(self.b, self.mu, use_graph=self.use_graph)
+        while t < self.ITER_MAX:
+            n = min(self.check_every, self.ITER_MAX - t)
+            cur.solver_step(n)
+            t += n
+            res = cur.duality_gap(screen=screen)
+            self.trace.append(dict(t=t, gap=res["gap"], primal=res["primal"], n_active=int(active.size)))
+            if bounded and res["gap"] <= target:
+                stopped = True
+                break
+            if t >= self.ITER_MAX or not screen:
+                continue
+            n_new = -(-max(res["n_keep"], 1) // q) * q
+            if n_new <= self.shrink * active.size:
+                t0 = time.time()
+                cur, x0, active = self._compact(cur, res, active, n_new)
+                cur.solver_reset(self.b, self.mu, x0=x0, use_graph=self.use_graph)
+                cur.stream.synchronize()
+                self.compact_seconds += time.time() - t0
+        x = np.zeros(K)
+        x[active] = cur.solver_x()
+        t_elapsed = time.time() - start
+        self.x = x.reshape(-1, 1)
+        # the certificate: the gap of that x on the full A (the original context)
+        gc = self.gpu_cal
+        gc.solver_reset(self.b, self.mu, x0=x, use_graph=False)
+        cert = gc.duality_gap(screen=False)
+        self.certificate = {k: cert[k] for k in ("primal", "dual", "gap", "scale", "gnorm_inf", "n_keep")}
+        self.iters = t
+        self.stopped = stopped
+        self.active = active
+        self.rlt_display(SILENCE, t_elapsed, t - 1)
         return t_elapsed
 
 

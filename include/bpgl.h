@@ -68,7 +68,9 @@ const char* bpgl_last_error(void);
  *   302 (0.3.2): RCCL row shards whose row needs more segment blocks than the stream's CUs run
  *                the two-pass row iteration instead of failing at bpgl_solver_reset; the panel's
  *                fused update is admitted against the stream's CUs; panel stat "fuse_cus"; tuning
- *                key and solver stat "onepass_sb1". */
+ *                key and solver stat "onepass_sb1".
+ *   303 (0.3.3): + bpgl_solver_gap (duality-gap certificate and gap-safe column screening) and
+ *                bpgl_gather_columns; bpgl_scratch_bytes grows by the gap's partials and counts. */
 int bpgl_version(void);
 
 /*
@@ -234,6 +236,40 @@ int bpgl_solver_status(bpgl_ctx* ctx, int64_t* iters_done, int* stopped, int64_t
                        double* gamma, double* err);
 int bpgl_solver_stat(bpgl_ctx* ctx, const char* key, int64_t* value);
 const double* bpgl_solver_residual(bpgl_ctx* ctx);
+
+/*
+ * Optimality certificate and gap-safe screening at the solver's current point (single rank, since
+ * ABI 303).  With r = A x - b, g = A^T r over ALL feature blocks and d_j = ||a_j||^2 (the diag):
+ *   primal = 1/2 ||r||^2 + mu ||x||_1
+ *   scale  = min(1, mu / ||g||_inf)  (1 when g = 0), so that theta = scale r is dual feasible
+ *   dual   = -1/2 scale^2 ||r||^2 - scale r.b
+ *   gap    = primal - dual >= P(x) - P*   (>= 0 up to rounding)
+ *   score_j = scale |g_j| + sqrt(d_j) sqrt(2 max(gap, 0));  score_j < mu proves x*_j = 0.
+ * g_all (device, nblock * w_pad fp64, required, caller-owned) receives g, block b at b * w_pad:
+ *   an exact A_b^T r per block (never the one-pass iteration's carried gradient).
+ * keep (device, nblock * w_pad bytes, may be NULL): keep[b * w_pad + j] = 1 unless score_j < mu
+ *   (so a NaN keeps every column); padding entries (j >= w) are 0 and never counted.
+ * out6 (host): [primal, dual, gap, scale, ||g||_inf, n_keep]; n_keep = nblock * w when keep is NULL.
+ * The call first does what bpgl_solver_status does (synchronises, re-runs iterations a failed
+ * one-pass launch lost), enqueues its work and synchronises again.  It is read-only for the
+ * solve: x, r, the carried gradient, the refresh schedule and every stat counter are unchanged,
+ * and its reductions have a fixed order (two calls on the same state return the same bits).
+ * BPGL_E_STATE: before bpgl_solver_reset, before a diag is installed, or on any multi-rank
+ * context (RCCL communicator, bpgl_set_ranks, row shards).
+ */
+int bpgl_solver_gap(bpgl_ctx* ctx, double* g_all, uint8_t* keep, double* out6);
+
+/*
+ * Column gather: A_out[i * lda_out + c] = A(i, cols[c]) for 0 <= c < n_out, in the context's
+ * dtype.  cols (device, n_out int32) holds global column indices b * w + j, resolved through
+ * the bound lda / block_stride, in any order; an index outside [0, nblock * w) (-1 by
+ * convention) writes 0, as do the columns c in [n_out, lda_out).  A_out: device, 16-byte
+ * aligned, row-major [m][lda_out], not overlapping A; lda_out >= n_out and a multiple of 16
+ * bytes' worth of elements (so A_out can be bound in place by a new context).  Enqueued on the
+ * context's stream; about one pass over A.  BPGL_E_ARG on bad arguments.
+ */
+int bpgl_gather_columns(bpgl_ctx* ctx, const int32_t* cols, int64_t n_out, void* A_out,
+                        int64_t lda_out);
 
 /*
  * One-call form: reset, run n_iter iterations, wait (bpgl_solver_status, so lost
