@@ -16,7 +16,9 @@ path (``gpu_calculation``) never calls them.
   fun_dd_p            cpu_calculation.py:49-50  (w, 1) -> (P, w/P, 1)
 
 New beside them (no counterpart in the reference): ``duality_gap`` and ``gap_safe_keep``, the
-numpy fp64 restatement of the device's optimality certificate and screening rule.
+numpy fp64 restatement of the device's optimality certificate and screening rule;
+``panel_duality_gap``, the same per right-hand side of a panel, and ``mu_grid``, the geometric grid
+of a regularization path.
 """
 import numpy as np
 
@@ -102,3 +104,25 @@ def gap_safe_keep(A, b, x, mu, return_score=False):
     score = t["scale"] * np.abs(g) + np.sqrt(np.square(A).sum(axis=0)) * radius
     keep = ~(score < float(mu))
     return (keep, score) if return_score else keep
+
+
+def panel_duality_gap(A, B, X, mu):
+    """``duality_gap`` and ``gap_safe_keep`` for every column k of B (m, k) and X (n, k) with mu[k]
+    (a scalar serves all): dict of (k,) arrays primal, dual, gap, scale, gnorm_inf, n_keep and
+    keep (k, n) bool -- the numpy restatement of bpgl_panel_gap."""
+    A = np.asarray(A, dtype=np.float64)
+    B = np.ascontiguousarray(np.asarray(B, dtype=np.float64).T)   # rows: contiguous columns, as a caller's own
+    X = np.ascontiguousarray(np.asarray(X, dtype=np.float64).T)   # per-column call would pass them
+    k = B.shape[0]
+    mu = np.broadcast_to(np.asarray(mu, dtype=np.float64), (k,))
+    cols = [duality_gap(A, B[j], X[j], mu[j]) for j in range(k)]
+    out = {key: np.array([c[key] for c in cols]) for key in ("primal", "dual", "gap", "scale", "gnorm_inf")}
+    out["keep"] = np.stack([gap_safe_keep(A, B[j], X[j], mu[j]) for j in range(k)])
+    out["n_keep"] = out["keep"].sum(axis=1).astype(np.int64)
+    return out
+
+
+def mu_grid(mu_max, n_mus, hi=0.9, lo=0.1):
+    """mu_max * geomspace(hi, lo, n_mus): a decreasing geometric grid below mu_max = ||A^T b||_inf
+    (at and above which x = 0 solves the problem)."""
+    return float(mu_max) * np.geomspace(hi, lo, int(n_mus))

@@ -20,6 +20,7 @@ __device__ __forceinline__ double wave_max(double v) {
     for (int o = 32; o > 0; o >>= 1) { double u = __shfl_xor(v, o); v = (u > v || u != u) ? u : v; }
     return v;
 }
+__device__ __forceinline__ double nan_max(double a, double b) { return (b > a || b != b) ? b : a; }
 
 __device__ __forceinline__ double soft_thr(double t, double tau) {   // cpu_calculation.py:5-6
     const double mag = fabs(t) - tau;

@@ -30,8 +30,6 @@ constexpr int kGapBlocks = kThreads;   // at most one partial per thread of k_ga
 // res: [0] primal, [1] dual, [2] gap, [3] scale, [4] ||g||_inf, [5] n_keep
 constexpr int kGapRes = 8;
 
-__device__ __forceinline__ double nan_max(double a, double b) { return (b > a || b != b) ? b : a; }
-
 // grid <= kGapBlocks blocks of kThreads; grid-stride over the m rows and the nblock * w_pad
 // column slots (padding slots j >= w take no part)
 __global__ __launch_bounds__(kThreads) void k_gap_partials(Params p, const double* __restrict__ g_all,

@@ -11,6 +11,7 @@
 #include "../../include/bpgl.h"
 #include "bpgl_host.h"
 #include "bpgl_panel.h"
+#include "bpgl_panel_gap.h"
 
 using namespace bpgl;
 using namespace bpgl_host;
@@ -46,6 +47,8 @@ struct bpgl_panel {
                                   // 1024 measured best with 512, +0.4 % over 256: profiles/r05/panel_fused)
     int64_t t_host = 0;           // iterations enqueued since the last reset
     int64_t n_exact = 0;          // carried gradient: exact-gradient iterations since the last reset
+    hipEvent_t gap_ev[3] = {};    // bpgl_panel_gap: before product 1, between the products, after product 2
+    int64_t gap_ns[2] = {};       // the last call's two products (each with its fold), stats "gap_prod1_ns" / "gap_prod2_ns"
     int64_t ldr() const { return m; }
     int64_t ldd() const { return w; }
 };
@@ -54,8 +57,34 @@ namespace {
 
 struct PanelLayout {
     int64_t st, Rh, Rl, Dh, Dl, X, Ax, B, R, diag, rec, Sslab, S, norms, lsp, mu, gamma, err_rhs, cnt, ready, lsdone, Gc,
-        Sh, Ec, At, A1t, total;
+        Sh, Ec, At, A1t, gpart, gparts, gcounts, gres, total;
 };
+// bpgl_panel_gap: the chunks of a product's reduction (`stages` 32-deep stages, `tiles` 64-output
+// tiles) -- doubled while the product has fewer than kPgBlocksTarget blocks and a chunk keeps two
+// stages.  A function of the shape alone.
+int pgap_split(int64_t tiles, int64_t stages) {
+    int spl = 1;
+    while (tiles * spl < kPgBlocksTarget && stages % (2 * spl) == 0 && stages / (2 * spl) >= 2) spl *= 2;
+    return spl;
+}
+int pgap_nparts(const bpgl_panel* c) {
+    return (int)std::min<int64_t>(cdiv(std::max<int64_t>(c->m, c->n), 4 * kThreads), kPgPartBlocks);
+}
+template <int PROD>
+int pgap_prod(bpgl_panel* c, const PanelGapArgs& a, dim3 grid) {
+    const dim3 blk(kThreads);
+    switch (c->k) {
+        case 16: hipLaunchKernelGGL((k_pgap_prod<1, PROD>), grid, blk, 0, c->stream, a); break;
+        case 32: hipLaunchKernelGGL((k_pgap_prod<2, PROD>), grid, blk, 0, c->stream, a); break;
+        case 64: hipLaunchKernelGGL((k_pgap_prod<4, PROD>), grid, blk, 0, c->stream, a); break;
+        default: hipLaunchKernelGGL((k_pgap_prod<8, PROD>), grid, blk, 0, c->stream, a); break;
+    }
+    LAUNCH_CHECK("k_pgap_prod");
+    const dim3 fgrid((unsigned)cdiv((int64_t)c->k * (PROD == 1 ? c->m : c->n), kThreads));
+    hipLaunchKernelGGL(k_pgap_fold<PROD>, fgrid, blk, 0, c->stream, a);
+    LAUNCH_CHECK("k_pgap_fold");
+    return 0;
+}
 PanelLayout panel_layout(const bpgl_panel* c) {
     Carve k;
     PanelLayout L;
@@ -88,6 +117,14 @@ PanelLayout panel_layout(const bpgl_panel* c) {
     L.Ec = k.take(carry ? 4 * km : 0);                           // its rounding error, fed into the next one (fp32)
     L.At = k.take(kPanelTiled2 ? 2 * c->m * c->n : 0);            // pass 2's tiled copy of A (bf16)
     L.A1t = k.take(kPanelTiled1 ? 2 * c->m * c->n : 0);           // pass 1's tiled copy of A (bf16)
+    // bpgl_panel_gap (bpgl_panel_gap.h): the two products' chunk partials (one buffer, the larger), the
+    // per-RHS partials, the screen's per-block counts and the results.  Laid out last: nothing before
+    // them moves.
+    const int64_t sp1 = pgap_split(c->m / kPgTile, c->n / kPgK), sp2 = pgap_split(c->n / kPgTile, c->m / kPgK);
+    L.gpart = k.take(8 * (int64_t)c->k * std::max(sp1 * c->m, sp2 * c->n));
+    L.gparts = k.take(8 * (int64_t)kPgPart * pgap_nparts(c) * c->k);
+    L.gcounts = k.take(4 * (int64_t)c->k * cdiv(c->n, kThreads));
+    L.gres = k.take(8 * (int64_t)kPgRes * c->k);
     L.total = k.off;
     return L;
 }
@@ -329,6 +366,8 @@ void bpgl_panel_destroy(bpgl_panel* c) {
     (void)hipSetDevice(c->device);   // destroy path: nothing to report to
     drop_graphs(c);
     for (auto e : c->evs) (void)hipEventDestroy(e);
+    for (auto e : c->gap_ev)
+        if (e) (void)hipEventDestroy(e);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -631,11 +670,82 @@ int bpgl_panel_stat(const bpgl_panel* c, const char* key, int64_t* value) {
     if (!strcmp(key, "iters_enqueued")) *value = c->t_host;
     else if (!strcmp(key, "exact_gradients")) *value = c->n_exact;
     else if (!strcmp(key, "fuse_cus")) *value = c->fuse_cus;   // CUs the fused-update check counted
+    else if (!strcmp(key, "gap_prod1_ns")) *value = c->gap_ns[0];   // the last bpgl_panel_gap: R_fresh = A X - B
+    else if (!strcmp(key, "gap_prod2_ns")) *value = c->gap_ns[1];   // ... and G = A^T R_fresh
     else return fail(BPGL_E_ARG, "unknown panel stat '%s'", key);
     return 0;
 }
 
 const double* bpgl_panel_residual(bpgl_panel* c) { return c ? c->p.R : nullptr; }
+
+int bpgl_panel_gap(bpgl_panel* c, double* G_all, double* R_fresh, uint8_t* keep, double* out) {
+    int rc;
+    if ((rc = panel_ready(c))) return rc;
+    if (!c->have_diag) return fail(BPGL_E_STATE, "bpgl_panel_diag must run before bpgl_panel_gap");
+    if (!c->solver) return fail(BPGL_E_STATE, "bpgl_panel_reset has not been called");
+    if (!G_all || !R_fresh || !out) return fail(BPGL_E_ARG, "G_all, R_fresh and out must be non-null");
+    if (((uintptr_t)G_all) % 16 || ((uintptr_t)R_fresh) % 16)
+        return fail(BPGL_E_ARG, "G_all and R_fresh must be 16-byte aligned");
+    if ((rc = bpgl_panel_status(c, nullptr, nullptr))) return rc;   // waits; reports a failed exchange
+    const PanelLayout L = panel_layout(c);
+    char* s = (char*)c->p.st - L.st;
+    double* parts = (double*)(s + L.gparts);
+    double* res = (double*)(s + L.gres);
+    int* counts = (int*)(s + L.gcounts);
+    PanelGapArgs a{};
+    a.A = c->p.A;
+    a.lda = c->p.lda;
+    a.m = c->m;
+    a.n = c->n;
+    a.w = c->w;
+    a.nblock = c->nblock;
+    a.k = c->k;
+    a.X = c->p.X;
+    a.B = c->p.B;
+    a.R = c->p.R;
+    a.diag = c->p.diag;
+    a.mu = c->p.mu;
+    a.Rf = R_fresh;
+    a.G = G_all;
+    a.part = (double*)(s + L.gpart);
+    for (auto& e : c->gap_ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipEventRecord(c->gap_ev[0], c->stream));
+    // product 1: Rf = A X - B; product 2: G = A^T Rf.  Reads X, B, R, diag, mu and A only; writes the
+    // caller's buffers and this call's own scratch.
+    for (int prod = 1; prod <= 2; ++prod) {
+        const int64_t len = prod == 1 ? c->m : c->n, stages = (prod == 1 ? c->n : c->m) / kPgK;
+        a.spl = pgap_split(len / kPgTile, stages);
+        a.chunk = stages / a.spl;
+        const dim3 grid((unsigned)(len / kPgTile * a.spl));
+        if ((rc = prod == 1 ? pgap_prod<1>(c, a, grid) : pgap_prod<2>(c, a, grid))) return rc;
+        HIP_TRY(hipEventRecord(c->gap_ev[prod], c->stream));
+    }
+    const int nparts = pgap_nparts(c);
+    hipLaunchKernelGGL(k_pgap_partials, dim3((unsigned)nparts, (unsigned)c->k), dim3(kThreads), 0, c->stream, a,
+                       parts);
+    LAUNCH_CHECK("k_pgap_partials");
+    hipLaunchKernelGGL(k_pgap_final, dim3((unsigned)c->k), dim3(kThreads), 0, c->stream, parts, nparts, a.mu, res);
+    LAUNCH_CHECK("k_pgap_final");
+    if (keep) {
+        const int64_t nb = cdiv(c->n, kThreads);
+        hipLaunchKernelGGL(k_pgap_screen, dim3((unsigned)nb, (unsigned)c->k), dim3(kThreads), 0, c->stream, a, res, keep,
+                           counts);
+        LAUNCH_CHECK("k_pgap_screen");
+        hipLaunchKernelGGL(k_pgap_count, dim3((unsigned)c->k), dim3(kThreads), 0, c->stream, counts, (long long)nb, res);
+        LAUNCH_CHECK("k_pgap_count");
+    }
+    HIP_TRY(hipMemcpyAsync(out, res, sizeof(double) * kPgRes * c->k, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int q = 0; q < 2; ++q) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, c->gap_ev[q], c->gap_ev[q + 1]));
+        c->gap_ns[q] = (int64_t)((double)ms * 1e6);
+    }
+    if (!keep)
+        for (int k = 0; k < c->k; ++k) out[(int64_t)k * kPgRes + 5] = (double)c->n;
+    return 0;
+}
 
 int bpgl_panel_geometry(const bpgl_panel* c, int32_t* kchunks) {
     if (!c) return fail(BPGL_E_ARG, "null panel context");

@@ -1,0 +1,310 @@
+// Panel duality-gap certificate.  Included by bpgl_panel_abi.hip only.
+// Checkpoint operations, not per-iteration ones.
+//
+// The certificate describes the STORED x (the solver's fp32 iterate), not the solver's carried
+// state.  bf16 A widens to fp64 exactly; everything after that is fp64:
+//   Rf[k][i]     = sum_j A[i][j] x_k[j] - B[k][i]          over all feature blocks   (product 1)
+//   G[blk][k][j] = sum_i A[i][blk w + j] Rf[k][i]          from Rf only              (product 2)
+// and per right-hand side k, with mu_k and d_j = ||a_j||^2 (the context's diag), the formulas of
+// bpgl_gap.h:
+//   primal, dual, gap, scale, ||g||_inf;  keep[k][j] = !(score_j < mu_k);  n_keep
+//   drift_k = max_i |R_solver[k][i] - Rf[k][i]|
+//
+//   k_pgap_prod<NT, PROD>   a 256-thread block owns 64 outputs x all 16 NT right-hand sides over one
+//                           chunk of the reduction; wave w owns 16 outputs x NT tiles of
+//                           v_mfma_f64_16x16x4_f64.  A travels global -> registers (16-byte pieces
+//                           along its contiguous dimension) -> LDS as fp64, the k-wide operand
+//                           (x, fp32, or Rf, fp64) likewise; the next stage's pieces are in
+//                           registers while this stage's MFMAs run.  Writes its chunk's partial.
+//   k_pgap_fold<PROD>       out = the chunks' partials added in chunk order (- B for product 1)
+//   k_pgap_partials         per (block, RHS): [sum r^2, sum r.b, sum |x|, max |g|, max |R - r|]
+//   k_pgap_final            one block per RHS: folds them in block order -> res[k][0..4], res[k][6]
+//   k_pgap_screen           keep[k][j] and per-block counts
+//   k_pgap_count            one block per RHS: res[k][5] = n_keep
+// Every reduction walks its dimension in a fixed order (within a chunk: 32-deep stages in index
+// order, 4 at a time through the MFMA; then the chunks; then wave_sum / wave_max, the waves, the
+// blocks in index order).  No floating-point atomics: two calls on the same state return the same
+// bits.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "bpgl_panel.h"
+
+namespace bpgl {
+
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+
+constexpr int kPgTile = 64;               // outputs per block
+constexpr int kPgK = 32;                  // reduction depth per stage
+// LDS row strides in doubles.  An MFMA operand read takes, per half-wave, rows i = 0..15 at depths
+// j, j + 1: [row][depth] images want stride = 2 (mod 32) and the [depth][row] image 16 (mod 32) for
+// 32 distinct 8-byte banks.
+constexpr int kPgLdV = kPgK + 2;          // k-wide operand  [rhs][depth]
+constexpr int kPgLdA1 = kPgK + 2;         // product 1's A   [output row][depth]
+constexpr int kPgLdA2 = kPgTile + 16;     // product 2's A   [depth][output column]
+constexpr int kPgBlocksTarget = 512;      // the reduction is split until a product has about this many blocks
+constexpr int kPgRes = 8;                 // res[k]: primal, dual, gap, scale, ||g||_inf, n_keep, drift, 0
+constexpr int kPgPart = 5;                // partials per (block, RHS)
+constexpr int kPgPartBlocks = kThreads;   // at most one partial per thread of k_pgap_final
+
+struct PanelGapArgs {
+    const __bf16* A;      // [m][lda]
+    long long lda, m, n, w;
+    int nblock, k;
+    const float* X;       // [nblock][k][w]   the solver's iterate
+    const double* B;      // [k][m]
+    const double* R;      // [k][m]           the solver's residual (drift only)
+    const double* diag;   // [n]
+    const double* mu;     // [k]
+    double* Rf;           // [k][m]           caller's
+    double* G;            // [nblock][k][w]   caller's
+    double* part;         // [spl][k][len]    a product's chunk partials
+    int spl;              // chunks of the product being run
+    long long chunk;      // stages per chunk
+};
+
+// bf16 e of 8 in a 16-byte piece -> fp64 (exact)
+__device__ __forceinline__ double pg_widen(const u32x4& v, int e) {
+    const unsigned word = v[e >> 1];
+    return (double)__uint_as_float((e & 1) ? (word & 0xffff0000u) : (word << 16));
+}
+
+// PROD 1: outputs = rows of A, depth = columns (A contiguous along the depth);
+// PROD 2: outputs = columns of A, depth = rows (A contiguous along the outputs).
+// grid = tiles * spl; block b: tile b % tiles, chunk b / tiles
+template <int NT, int PROD>
+__global__ __launch_bounds__(kThreads) void k_pgap_prod(PanelGapArgs a) {
+    constexpr int K = 16 * NT;
+    constexpr int NV = PROD == 1 ? (NT + 1) / 2 : NT;   // 16-byte pieces of the k-wide operand per thread and stage
+    constexpr int VP = PROD == 1 ? 8 : 16;              // ... per right-hand side
+    __shared__ __attribute__((aligned(16))) double As[PROD == 1 ? kPgTile * kPgLdA1 : kPgK * kPgLdA2];
+    __shared__ __attribute__((aligned(16))) double Vs[K * kPgLdV];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long len = PROD == 1 ? a.m : a.n;
+    const long long tiles = len / kPgTile;
+    const long long tile = blockIdx.x % tiles;
+    const long long c = blockIdx.x / tiles;
+    const long long o0 = tile * kPgTile;
+    const long long s0 = c * a.chunk, s1 = s0 + a.chunk;
+
+    u32x4 ra, rv[NV];
+    auto fetch = [&](long long s) {
+        const long long d0 = s * kPgK;
+        if (PROD == 1) {
+            ra = *reinterpret_cast<const u32x4*>(a.A + (o0 + (tid >> 2)) * a.lda + d0 + (tid & 3) * 8);
+            const long long blk = d0 / a.w, jj = d0 % a.w;
+#pragma unroll
+            for (int q = 0; q < NV; ++q) {
+                const int p = tid + kThreads * q;
+                if (p < K * VP)
+                    rv[q] = *reinterpret_cast<const u32x4*>(a.X + (blk * K + (p >> 3)) * a.w + jj + (p & 7) * 4);
+            }
+        } else {
+            ra = *reinterpret_cast<const u32x4*>(a.A + (d0 + (tid >> 3)) * a.lda + o0 + (tid & 7) * 8);
+#pragma unroll
+            for (int q = 0; q < NV; ++q) {
+                const int p = tid + kThreads * q;
+                rv[q] = *reinterpret_cast<const u32x4*>(a.Rf + (long long)(p >> 4) * a.m + d0 + (p & 15) * 2);
+            }
+        }
+    };
+    auto stash = [&]() {
+        double* ad = PROD == 1 ? As + (tid >> 2) * kPgLdA1 + (tid & 3) * 8 : As + (tid >> 3) * kPgLdA2 + (tid & 7) * 8;
+#pragma unroll
+        for (int e = 0; e < 8; e += 2) {
+            f64x2 v;
+            v[0] = pg_widen(ra, e);
+            v[1] = pg_widen(ra, e + 1);
+            *reinterpret_cast<f64x2*>(ad + e) = v;
+        }
+#pragma unroll
+        for (int q = 0; q < NV; ++q) {
+            const int p = tid + kThreads * q;
+            if (PROD == 1) {
+                if (p < K * VP) {
+                    double* vd = Vs + (p >> 3) * kPgLdV + (p & 7) * 4;
+                    f64x2 lo, hi;
+                    lo[0] = (double)__uint_as_float(rv[q][0]);
+                    lo[1] = (double)__uint_as_float(rv[q][1]);
+                    hi[0] = (double)__uint_as_float(rv[q][2]);
+                    hi[1] = (double)__uint_as_float(rv[q][3]);
+                    *reinterpret_cast<f64x2*>(vd) = lo;
+                    *reinterpret_cast<f64x2*>(vd + 2) = hi;
+                }
+            } else {
+                union { u32x4 q; f64x2 d; } u;
+                u.q = rv[q];
+                *reinterpret_cast<f64x2*>(Vs + (p >> 4) * kPgLdV + (p & 15) * 2) = u.d;
+            }
+        }
+    };
+
+    f64x4 acc[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
+    const int li = lane & 15, lj = lane >> 4;
+    fetch(s0);
+    for (long long s = s0; s < s1; ++s) {
+        __syncthreads();          // the previous stage's reads are done
+        stash();
+        __syncthreads();
+        if (s + 1 < s1) fetch(s + 1);
+#pragma unroll
+        for (int d = 0; d < kPgK; d += 4) {
+            // the MFMA's "A" operand is the k-wide one (its rows = right-hand sides) and its "B" operand
+            // the matrix (its columns = outputs): D[row = rhs][col = output], so a lane's results sit
+            // at one output and 16 lanes store 128 contiguous bytes
+            const double bv = PROD == 1 ? As[(16 * wave + li) * kPgLdA1 + d + lj]
+                                        : As[(d + lj) * kPgLdA2 + 16 * wave + li];
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const double av = Vs[(16 * t + li) * kPgLdV + d + lj];
+                acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc[t], 0, 0, 0);
+            }
+        }
+    }
+    // C/D of v_mfma_f64_16x16x4_f64: col = lane & 15, row = (lane >> 4) + 4 reg
+    double* dst = a.part + (c * K) * len + o0 + 16 * wave + li;
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dst[(long long)(16 * t + lj + 4 * r) * len] = acc[t][r];
+}
+
+// one thread per (rhs, output): the chunks in index order; product 1 subtracts B and writes Rf[k][i],
+// product 2 writes G[blk][k][j]
+template <int PROD>
+__global__ __launch_bounds__(kThreads) void k_pgap_fold(PanelGapArgs a) {
+    const long long len = PROD == 1 ? a.m : a.n;
+    const long long e = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (e >= (long long)a.k * len) return;
+    const long long k = e / len, o = e % len;
+    double v = a.part[e];
+    for (int c = 1; c < a.spl; ++c) v += a.part[(long long)c * a.k * len + e];
+    if (PROD == 1) a.Rf[e] = v - a.B[e];
+    else a.G[((o / a.w) * a.k + k) * a.w + o % a.w] = v;
+}
+
+// grid (nparts, k); parts[k][nparts][kPgPart]
+__global__ __launch_bounds__(kThreads) void k_pgap_partials(PanelGapArgs a, double* __restrict__ parts) {
+    const int k = blockIdx.y;
+    const long long tid = (long long)blockIdx.x * kThreads + threadIdx.x;
+    const long long stride = (long long)gridDim.x * kThreads;
+    double rr = 0.0, rb = 0.0, ax = 0.0, gm = 0.0, dr = 0.0;
+    const double* __restrict__ rf = a.Rf + (long long)k * a.m;
+    const double* __restrict__ b = a.B + (long long)k * a.m;
+    const double* __restrict__ rs = a.R + (long long)k * a.m;
+    for (long long i = tid; i < a.m; i += stride) {
+        const double r = rf[i];
+        rr = fma(r, r, rr);
+        rb = fma(r, b[i], rb);
+        dr = nan_max(dr, fabs(rs[i] - r));
+    }
+    for (long long j = tid; j < a.n; j += stride) {
+        const long long e = ((j / a.w) * a.k + k) * a.w + j % a.w;
+        ax += fabs((double)a.X[e]);
+        gm = nan_max(gm, fabs(a.G[e]));
+    }
+    rr = wave_sum(rr);
+    rb = wave_sum(rb);
+    ax = wave_sum(ax);
+    gm = wave_max(gm);
+    dr = wave_max(dr);
+    __shared__ double red[kPgPart][kWaves];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) { red[0][wave] = rr; red[1][wave] = rb; red[2][wave] = ax; red[3][wave] = gm; red[4][wave] = dr; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double* dst = parts + ((long long)k * gridDim.x + blockIdx.x) * kPgPart;
+        for (int q = 0; q < 3; ++q) dst[q] = ((red[q][0] + red[q][1]) + red[q][2]) + red[q][3];
+        for (int q = 3; q < 5; ++q)
+            dst[q] = nan_max(nan_max(nan_max(red[q][0], red[q][1]), red[q][2]), red[q][3]);
+    }
+}
+
+// one block per RHS; thread q holds partial q (nparts <= kPgPartBlocks = kThreads).  The formulas and
+// the NaN behaviour of k_gap_final.
+__global__ __launch_bounds__(kThreads) void k_pgap_final(const double* __restrict__ parts, int nparts,
+                                                         const double* __restrict__ mu_all,
+                                                         double* __restrict__ res_all) {
+    const int k = blockIdx.x, q = threadIdx.x;
+    const bool ok = q < nparts;
+    const double* src = parts + ((long long)k * nparts + q) * kPgPart;
+    double rr = ok ? src[0] : 0.0;
+    double rb = ok ? src[1] : 0.0;
+    double ax = ok ? src[2] : 0.0;
+    double gm = ok ? src[3] : 0.0;
+    double dr = ok ? src[4] : 0.0;
+    rr = wave_sum(rr);
+    rb = wave_sum(rb);
+    ax = wave_sum(ax);
+    gm = wave_max(gm);
+    dr = wave_max(dr);
+    __shared__ double red[kPgPart][kWaves];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) { red[0][wave] = rr; red[1][wave] = rb; red[2][wave] = ax; red[3][wave] = gm; red[4][wave] = dr; }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    rr = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
+    rb = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+    ax = ((red[2][0] + red[2][1]) + red[2][2]) + red[2][3];
+    gm = nan_max(nan_max(nan_max(red[3][0], red[3][1]), red[3][2]), red[3][3]);
+    dr = nan_max(nan_max(nan_max(red[4][0], red[4][1]), red[4][2]), red[4][3]);
+    const double mu = mu_all[k];
+    const double primal = 0.5 * rr + mu * ax;
+    double s = 1.0;                       // also for g = 0 and for a NaN
+    if (gm > 0.0) { s = mu / gm; s = s < 1.0 ? s : 1.0; }
+    const double dual = -0.5 * s * s * rr - s * rb;
+    double* res = res_all + (long long)k * kPgRes;
+    res[0] = primal;
+    res[1] = dual;
+    res[2] = primal - dual;
+    res[3] = s;
+    res[4] = gm;
+    res[5] = 0.0;
+    res[6] = dr;
+    res[7] = 0.0;
+}
+
+// grid (ceil(n / kThreads), k): keep[k][j] for the global column j; counts[k][block] = columns kept
+__global__ __launch_bounds__(kThreads) void k_pgap_screen(PanelGapArgs a, const double* __restrict__ res_all,
+                                                          unsigned char* __restrict__ keep,
+                                                          int* __restrict__ counts) {
+    const int k = blockIdx.y;
+    const long long j = (long long)blockIdx.x * kThreads + threadIdx.x;
+    bool kp = false;
+    if (j < a.n) {
+        const double* res = res_all + (long long)k * kPgRes;
+        const double gap = res[2], s = res[3];
+        const double gp = gap < 0.0 ? 0.0 : gap;   // a NaN stays a NaN
+        const double g = a.G[((j / a.w) * a.k + k) * a.w + j % a.w];
+        const double score = s * fabs(g) + sqrt(a.diag[j]) * sqrt(2.0 * gp);
+        kp = !(score < a.mu[k]);
+        keep[(long long)k * a.n + j] = kp ? 1 : 0;
+    }
+    const int cnt = __popcll(__ballot(kp));
+    __shared__ int red[kWaves];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) red[wave] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) counts[(long long)k * gridDim.x + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// one block per RHS: res[k][5] = sum of its per-block counts (integers: exact in any order)
+__global__ __launch_bounds__(kThreads) void k_pgap_count(const int* __restrict__ counts, long long nblocks,
+                                                         double* __restrict__ res_all) {
+    const int k = blockIdx.x;
+    long long s = 0;
+    for (long long q = threadIdx.x; q < nblocks; q += kThreads) s += counts[(long long)k * nblocks + q];
+    __shared__ long long red[kThreads];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    long long tot = 0;
+    for (int q = 0; q < kThreads; ++q) tot += red[q];
+    res_all[(long long)k * kPgRes + 5] = (double)tot;
+}
+
+}  // namespace bpgl

@@ -27,6 +27,10 @@ runs the forms follow different trajectories to the same fixed point: x within
 1e-2 and the objective within 1e-4 on the default path (tests/test_panel.py;
 1e-5 for the exact-gradient hi + lo form).
 
+``PanelLasso.duality_gap`` certifies the stored fp32 x of every right-hand side (fp64 products on
+the bf16 A), and ``lasso_path`` runs one b against a grid of mu as one panel
+with that certificate as its stopping rule.
+
 All compute goes through libbpgl.so (bpgl_panel_* in include/bpgl.h).
 """
 import contextlib
@@ -59,6 +63,7 @@ _PANEL_SIGS = {
     "bpgl_panel_get_tuning": (ctypes.c_int, [_p, ctypes.c_char_p, ctypes.POINTER(_i64)]),
     "bpgl_panel_stat": (ctypes.c_int, [_p, ctypes.c_char_p, ctypes.POINTER(_i64)]),
     "bpgl_panel_residual": (_p, [_p]),
+    "bpgl_panel_gap": (ctypes.c_int, [_p, _p, _p, _p, ctypes.POINTER(ctypes.c_double)]),
 }
 N._SIGS.update(_PANEL_SIGS)
 
@@ -225,7 +230,8 @@ class PanelLasso:
         return v.value
 
     def stat(self, key):
-        """Counter since the last reset: "iters_enqueued", "exact_gradients"."""
+        """Counter since the last reset: "iters_enqueued", "exact_gradients"; of the last duality_gap,
+        its two products' device times: "gap_prod1_ns", "gap_prod2_ns"."""
         v = ctypes.c_int64()
         N.check(_lib().bpgl_panel_stat(self._ctx, key.encode(), ctypes.byref(v)), "bpgl_panel_stat")
         return v.value
@@ -236,6 +242,33 @@ class PanelLasso:
         off = addr - self._scratch.data_ptr()
         assert off % 8 == 0
         return self._scratch[off // 8: off // 8 + self.nrhs * self.MAT_HEIGHT].view(self.nrhs, self.MAT_HEIGHT)
+
+    GAP_KEYS = ("primal", "dual", "gap", "scale", "gnorm_inf", "n_keep", "drift")
+
+    def duality_gap(self, screen=True):
+        """Per-RHS optimality certificate of the stored fp32 x (include/bpgl.h bpgl_panel_gap): a dict of
+        (k,) numpy arrays primal, dual, gap, scale, gnorm_inf, n_keep (int64), drift, and the device
+        tensors g (k, n) fp64 = A^T r, r (k, m) fp64 = A x - b recomputed from x, keep (k, n) bool
+        (None when ``screen`` is false; n_keep is then n).  drift is max |solver residual - r| per RHS.
+        Read-only for the solve and bitwise repeatable.  The tensors are views of buffers the next call
+        overwrites (g is a copy when there is more than one feature block)."""
+        k, n, m = self.nrhs, self.MAT_WIDTH_ALL, self.MAT_HEIGHT
+        if getattr(self, "_gap_g", None) is None:
+            self._gap_g = torch.empty((self.Block, k, self.MAT_WIDTH), dtype=torch.float64, device=self.device)
+            self._gap_r = torch.empty((k, m), dtype=torch.float64, device=self.device)
+            self._gap_keep = torch.empty((k, n), dtype=torch.uint8, device=self.device)
+            self._gap_out = (ctypes.c_double * (8 * k))()
+        with self._on_stream():
+            N.check(_lib().bpgl_panel_gap(self._ctx, N.ptr(self._gap_g), N.ptr(self._gap_r),
+                                          N.ptr(self._gap_keep) if screen else None, self._gap_out),
+                    "bpgl_panel_gap")
+        out = np.array(self._gap_out, dtype=np.float64).reshape(k, 8)
+        res = {key: out[:, i].copy() for i, key in enumerate(self.GAP_KEYS)}
+        res["n_keep"] = res["n_keep"].astype(np.int64)
+        res["g"] = self._gap_g.permute(1, 0, 2).reshape(k, n)
+        res["r"] = self._gap_r
+        res["keep"] = self._gap_keep.view(torch.bool) if screen else None
+        return res
 
     def set_kernel_timing(self, enable):
         N.check(_lib().bpgl_panel_set_kernel_timing(self._ctx, int(bool(enable))), "bpgl_panel_set_kernel_timing")
@@ -256,3 +289,80 @@ class PanelLasso:
             self.stream.synchronize()
             out["err_iter"] = self._err_iter.cpu().numpy().copy()
         return out
+
+
+PANEL_NRHS = (16, 32, 64, 128)
+# lasso_path's default: the smallest multiple of 64 iterations at which one certificate costs at most
+# 10 % of the iterations between two of them, measured at 8192 x 65536, k = 128
+PATH_CHECK_EVERY = 192
+
+
+def pad_mus(mus):
+    """(padded grid, number given): 1 <= len(mus) <= 128 values of mu padded to the next panel width
+    (16, 32, 64 or 128) by repeating the largest given one, so the pad columns are duplicates of a
+    real problem.  More than 128 raise ValueError."""
+    mus = np.asarray(mus, dtype=np.float64).reshape(-1)
+    if not 1 <= mus.size <= PANEL_NRHS[-1]:
+        raise ValueError(f"lasso_path takes 1 to {PANEL_NRHS[-1]} values of mu (got {mus.size})")
+    k = next(v for v in PANEL_NRHS if v >= mus.size)
+    return np.concatenate([mus, np.full(k - mus.size, mus.max())]), int(mus.size)
+
+
+def lasso_path(A, b, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_BOUND=1e-4, ITER_MAX=4096,
+               check_every=PATH_CHECK_EVERY, device=None):
+    """A regularization path as ONE panel: min 1/2 ||A x - b||^2 + mu ||x||_1 for every mu of a grid,
+    on the bf16-stored A, every column of the panel holding the same b.
+
+    ``mus``: 1 to 128 values (ValueError above that), padded to the next panel width by repeating the
+    largest; the pad columns are dropped from every output.  ``mus=None``: mu_max = ||A^T b||_inf for
+    the stored bf16 A, read off a certificate taken right after a reset (x = 0, so gnorm_inf is
+    mu_max), then ``cpu_calculation.mu_grid(mu_max, n_mus, hi, lo)`` and a second reset.
+
+    The loop runs ``check_every`` iterations (block updates), then ``PanelLasso.duality_gap``; it
+    stops at the first check where every mu has gap <= GAP_BOUND * 1/2 ||b||^2 (ClassLassoScreened's
+    criterion), or after ITER_MAX iterations.  No compaction and no warm start: every mu starts at
+    x = 0 and runs until the slowest is done.  GAP_BOUND below about 1e-6 is out of reach of the fp32
+    x.
+
+    Returns a dict: x (n, len(mus)), mus, mu_max (None when mus was given), iters, reached (bool per
+    mu), first_reached (the iteration of the first check at which that mu met the bound, else -1), and
+    the last certificate's primal, dual, gap, scale, gnorm_inf, n_keep, drift per mu."""
+    from .cpu_calculation import mu_grid
+    if int(check_every) <= 0:
+        raise ValueError("check_every must be > 0")
+    b = np.asarray(b.detach().cpu() if isinstance(b, torch.Tensor) else b, dtype=np.float64).reshape(-1)
+    if mus is None:
+        if not 1 <= int(n_mus) <= PANEL_NRHS[-1]:
+            raise ValueError(f"lasso_path takes 1 to {PANEL_NRHS[-1]} values of mu (got {n_mus})")
+        grid, n_given = None, int(n_mus)
+        k = next(v for v in PANEL_NRHS if v >= n_given)
+    else:
+        grid, n_given = pad_mus(mus)
+        k = grid.size
+    pl = PanelLasso(A, Block, nrhs=k, device=device)
+    B = np.repeat(b[:, None], k, axis=1)
+    mu_max = None
+    if grid is None:
+        pl.solver_reset(B, 1.0)
+        mu_max = float(pl.duality_gap(screen=False)["gnorm_inf"][0])
+        grid, _ = pad_mus(mu_grid(mu_max, n_given, hi, lo))
+    pl.solver_reset(B, grid)
+    target = float(GAP_BOUND) * 0.5 * float(b @ b)
+    first = np.full(k, -1, dtype=np.int64)
+    t, cert = 0, None
+    while t < int(ITER_MAX):
+        step = min(int(check_every), int(ITER_MAX) - t)
+        pl.solver_step(step)
+        t += step
+        cert = pl.duality_gap(screen=True)
+        ok = cert["gap"] <= target
+        first[ok & (first < 0)] = t
+        if ok.all():
+            break
+    if cert is None:
+        cert = pl.duality_gap(screen=True)
+    out = dict(x=pl.solver_x()[:, :n_given], mus=grid[:n_given].copy(), mu_max=mu_max, iters=t,
+               reached=(cert["gap"] <= target)[:n_given], first_reached=first[:n_given])
+    for key in PanelLasso.GAP_KEYS:
+        out[key] = cert[key][:n_given]
+    return out

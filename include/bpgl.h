@@ -70,7 +70,10 @@ const char* bpgl_last_error(void);
  *                fused update is admitted against the stream's CUs; panel stat "fuse_cus"; tuning
  *                key and solver stat "onepass_sb1".
  *   303 (0.3.3): + bpgl_solver_gap (duality-gap certificate and gap-safe column screening) and
- *                bpgl_gather_columns; bpgl_scratch_bytes grows by the gap's partials and counts. */
+ *                bpgl_gather_columns; bpgl_scratch_bytes grows by the gap's partials and counts.
+ *   304 (0.3.4): + bpgl_panel_gap (the panel's per-RHS duality-gap certificate, gap-safe screen and
+ *                residual drift, from fp64 products on the stored x); bpgl_panel_scratch_bytes grows
+ *                by its partials. */
 int bpgl_version(void);
 
 /*
@@ -424,11 +427,39 @@ int bpgl_panel_set_tuning(bpgl_panel* ctx, const char* key, int64_t value);
 int bpgl_panel_get_tuning(const bpgl_panel* ctx, const char* key, int64_t* value);
 int bpgl_panel_geometry(const bpgl_panel* ctx, int32_t* kchunks);
 /* Counters since the last reset: "iters_enqueued", "exact_gradients" (carried
- * gradient: iterations whose pass 1 computed G = A^T R exactly -- every g_refresh-th). */
+ * gradient: iterations whose pass 1 computed G = A^T R exactly -- every g_refresh-th).
+ * Of the last bpgl_panel_gap (HIP events, nanoseconds): "gap_prod1_ns", "gap_prod2_ns". */
 int bpgl_panel_stat(const bpgl_panel* ctx, const char* key, int64_t* value);
 /* The solver's fp64 residual R = A X - B, [nrhs][m] in device memory (valid after
  * the stream has drained). */
 const double* bpgl_panel_residual(bpgl_panel* ctx);
+/*
+ * Optimality certificate of the STORED iterate, per right-hand side (since ABI 304).  The fp32 x of
+ * every feature block and the bf16 A (read from the caller's row-major image, widened to fp64, which
+ * is exact) enter two fp64 panel products (v_mfma_f64_16x16x4_f64):
+ *   R_fresh[k][i]  = sum_j A[i][j] x_k[j] - B[k][i]        (all feature blocks)
+ *   G_all[b][k][j] = sum_i A[i][b w + j] R_fresh[k][i]     (from R_fresh: never the solver's R, its
+ *                                                          bf16 images or the carried gradient)
+ * and, with mu_k and d_j = ||a_j||^2 (the diag), the formulas of bpgl_solver_gap above give per k
+ *   out[8 k + 0..7] = primal, dual, gap, scale, ||g||_inf, n_keep, drift, 0
+ * with drift_k = max_i |R[k][i] - R_fresh[k][i]| against the solver's recurrence residual.
+ * G_all (device, [nblock][nrhs][w] fp64) and R_fresh (device, [nrhs][m] fp64): required, 16-byte
+ *   aligned, caller-owned.
+ * keep (device, [nrhs][n] bytes, may be NULL): keep[k][j] = 1 unless score_j < mu_k (a NaN keeps every
+ *   column); n_keep = n when keep is NULL.
+ * out: host, nrhs x 8 doubles.
+ * The call first does what bpgl_panel_status does (synchronises; BPGL_E_EXCHANGE as there), enqueues
+ * on the context's stream and synchronises again.  It relies on bpgl_panel_step having applied the
+ * deferred x update (it always has).  Read-only for the solve: X, R and its bf16 images, the
+ * direction images, the carried gradient and its operands, the iteration and exact-gradient counters,
+ * the device state, the captured graphs and the solver's validity are untouched, so a following
+ * bpgl_panel_step continues bitwise as if the call had not happened.  Every reduction has a fixed
+ * order and there are no floating-point atomics: two calls on the same state return the same bits.
+ * Cost: 2 m n nrhs fp64 multiply-adds -- checkpoint work, not per-iteration work.
+ * BPGL_E_STATE before bpgl_panel_reset or before bpgl_panel_diag; BPGL_E_ARG on a null or misaligned
+ * required pointer.
+ */
+int bpgl_panel_gap(bpgl_panel* ctx, double* G_all, double* R_fresh, uint8_t* keep, double* out);
 
 #ifdef __cplusplus
 }
