@@ -18,7 +18,8 @@ path (``gpu_calculation``) never calls them.
 New beside them (no counterpart in the reference): ``duality_gap`` and ``gap_safe_keep``, the
 numpy fp64 restatement of the device's optimality certificate and screening rule;
 ``panel_duality_gap``, the same per right-hand side of a panel, and ``mu_grid``, the geometric grid
-of a regularization path.
+of a regularization path; ``kfold_masks``, ``masked_panel_iterate`` and ``masked_duality_gap``, the
+restatement of the panel's row-masked problems (K-fold cross-validation).
 """
 import numpy as np
 
@@ -126,3 +127,82 @@ def mu_grid(mu_max, n_mus, hi=0.9, lo=0.1):
     """mu_max * geomspace(hi, lo, n_mus): a decreasing geometric grid below mu_max = ||A^T b||_inf
     (at and above which x = 0 solves the problem)."""
     return float(mu_max) * np.geomspace(hi, lo, int(n_mus))
+
+
+# ---------------------------------------------------------------------------
+# Row masks (DESIGN.md section 11): min 1/2 || w o (A x - b) ||^2 + mu ||x||_1 with 0/1 row weights w,
+# the host restatement of bpgl_panel_set_row_mask's solver and certificate.
+# ---------------------------------------------------------------------------
+def kfold_masks(m, n_folds, seed=0):
+    """(n_folds, m) uint8: mask[f, i] = 0 where row i is held out of fold f, else 1.  The held-out sets
+    are the strides perm[f::n_folds] of RandomState(seed).permutation(m), so every row is held out
+    exactly once and the sets differ in size by at most one."""
+    m, n_folds = int(m), int(n_folds)
+    if not 2 <= n_folds <= m:
+        raise ValueError("n_folds must be between 2 and m")
+    perm = np.random.RandomState(int(seed)).permutation(m)
+    masks = np.ones((n_folds, m), dtype=np.uint8)
+    for f in range(n_folds):
+        masks[f, perm[f::n_folds]] = 0
+    return masks
+
+
+def masked_panel_iterate(A, b, w, mu, Block, iters, diag=None, x0=None):
+    """``iters`` block updates (cyclic over ``Block`` feature blocks) of the panel's iteration on the
+    masked problem of one right-hand side, in fp64: with R = w o (A x - b), G = A_m^T R, the shrink
+    x^ = S(x - G / d, mu / d), D = x^ - x, S = w o (A_m D), the exact line search along D and
+    x += gamma D.  ``diag``: the d_j > 0 of the shrink, (n,); default the FULL column norms ||a_j||^2,
+    as the device uses (not those of the masked rows).  Returns dict(x, r) with r the masked residual."""
+    A = np.asarray(A, dtype=np.float64)
+    m, n = A.shape
+    Block = int(Block)
+    wd = n // Block
+    b = np.asarray(b, dtype=np.float64).reshape(-1)
+    w = (np.asarray(w).reshape(-1) != 0).astype(np.float64)
+    mu = float(mu)
+    dg = np.square(A).sum(axis=0) if diag is None else np.asarray(diag, dtype=np.float64).reshape(-1)
+    dg = dg.reshape(Block, wd)
+    x = (np.zeros(n) if x0 is None else np.array(x0, dtype=np.float64).reshape(-1)).reshape(Block, wd).copy()
+    Ax = np.stack([w * (A[:, q * wd:(q + 1) * wd] @ x[q]) for q in range(Block)])
+    wb = w * b
+    for t in range(int(iters)):
+        mb = t % Block
+        Am = A[:, mb * wd:(mb + 1) * wd]
+        r = Ax.sum(axis=0) - wb
+        g = Am.T @ r
+        rx = dg[mb] * x[mb] - g
+        Bx = (1.0 / dg[mb]) * (np.sign(rx) * np.maximum(np.abs(rx) - mu, 0))
+        D = Bx - x[mb]
+        s = w * (Am @ D)
+        r1 = r @ s + mu * (np.abs(Bx).sum() - np.abs(x[mb]).sum())
+        r2 = s @ s
+        gamma = 0.0 if r2 == 0 else float(np.clip(-r1 / r2, 0, 1))
+        x[mb] += gamma * D
+        Ax[mb] += gamma * s
+    return dict(x=x.reshape(-1), r=Ax.sum(axis=0) - wb)
+
+
+def masked_duality_gap(A, b, w, x, mu, diag=None):
+    """The certificate of ``duality_gap`` on the masked problem: r = w o (A x - b), g = A^T r, and
+    primal, dual, gap, scale, gnorm_inf from them (b enters through r . b, where the held-out rows
+    of r are 0).  Also holdout_sse = sum (1 - w)(A x - b)^2, and the gap-safe score and keep with
+    ``diag`` (default the FULL column norms: d_j >= ||w o a_j||^2, so the rule stays safe)."""
+    A = np.asarray(A, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64).reshape(-1)
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    w = (np.asarray(w).reshape(-1) != 0).astype(np.float64)
+    mu = float(mu)
+    e = A @ x - b
+    r = w * e
+    g = A.T @ r
+    rr = float(r @ r)
+    primal = 0.5 * rr + mu * float(np.abs(x).sum())
+    gn = float(np.max(np.abs(g)))
+    scale = min(1.0, mu / gn) if gn > 0.0 else 1.0
+    dual = -0.5 * scale * scale * rr - scale * float(r @ b)
+    gap = primal - dual
+    h = (1.0 - w) * e
+    dg = np.square(A).sum(axis=0) if diag is None else np.asarray(diag, dtype=np.float64).reshape(-1)
+    score = scale * np.abs(g) + np.sqrt(dg) * np.sqrt(2.0 * np.maximum(gap, 0.0))
+    return dict(primal=primal, dual=dual, gap=gap, scale=scale, gnorm_inf=gn, holdout_sse=float(h @ h),
+                score=score, keep=~(score < mu), g=g, r=r)

@@ -109,7 +109,16 @@ struct PanelParams {
     // k_panel_reduce_upd (the reduce, line search and residual update in one launch)
     unsigned long long* ready;   // [k] per RHS: the arrival count at which its step size was published
     unsigned long long* lsdone;  // line searches finished (monotone, + k per launch): the last one bumps t
+    // row mask (bpgl_panel_set_row_mask): only the masked (MK) kernel variants read it
+    const unsigned char* W;      // [k][m] nonzero: the row is in that RHS's objective; null without a mask
 };
+
+// a thread's 4 consecutive rows of a masked RHS: the slab sums of held-out rows become 0 by select
+// (never by multiply), so an all-ones mask leaves every bit as the unmasked kernels have it
+__device__ __forceinline__ void panel_mask4(unsigned wv, double (&s)[4]) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) s[q] = ((wv >> (8 * q)) & 0xffu) ? s[q] : 0.0;
+}
 
 constexpr int kLspRows = 1024;    // rows per line-search partial
 
@@ -944,6 +953,9 @@ __device__ __forceinline__ void panel_norm_share(const PanelParams& p, int rhs, 
 // 1024-row group (mode 1), or plain output (mode 0, API).  grid = k x (m / 1024);
 // a thread owns 4 consecutive rows (16-B slab loads).  Mode 1: the last block of an RHS to
 // finish runs that RHS's line search (panel_step_rhs), so no separate step launch.
+// MK (mode 1 only): the masked fold -- S becomes w o S (panel_mask4) before it is stored and before
+// the line-search partials, so the update kernels see the masked S and need no mask of their own.
+template <bool MK>
 __global__ __launch_bounds__(kThreads) void k_panel_reduce(PanelParams p, double* __restrict__ Sout, int mode) {
     const int rhs = blockIdx.x % p.k;
     const int grp = blockIdx.x / p.k;
@@ -960,6 +972,8 @@ __global__ __launch_bounds__(kThreads) void k_panel_reduce(PanelParams p, double
         const double2 r23 = *reinterpret_cast<const double2*>(rp + 2);
         const float* src = p.Sslab + (long long)rhs * p.m + i;
         const long long cstride = (long long)p.k * p.m;
+        unsigned wv = 0;
+        if constexpr (MK) wv = *reinterpret_cast<const unsigned*>(p.W + (long long)rhs * p.m + i);
         auto add = [&](const float4& v) {
             s[0] += (double)v.x;
             s[1] += (double)v.y;
@@ -978,6 +992,7 @@ __global__ __launch_bounds__(kThreads) void k_panel_reduce(PanelParams p, double
             for (int q = 0; q < 8; ++q) add(v[q]);
         }
         for (; c < p.kchunks; ++c) add(*reinterpret_cast<const float4*>(src + c * cstride));
+        if constexpr (MK) panel_mask4(wv, s);
         const long long e = (long long)rhs * p.m + i;
         put(Sout, e, make_double2(s[0], s[1]));
         put(Sout, e + 2, make_double2(s[2], s[3]));
@@ -1228,8 +1243,11 @@ __global__ __launch_bounds__(kThreads) void k_panel_update1(PanelParams p, int c
 // a wait that runs out sets PanelState::fail, updates nothing, and bpgl_panel_status reports it.
 // The last line search to finish (lsdone) ends the iteration as k_panel_update1 does (t + 1, the
 // error record, x pending).
+// MK: the masked fold of k_panel_reduce<true> (one 32-bit word of 4 mask bytes per 1024-row group,
+// S zeroed by select before the partials, the carried operand and the R update); same grid, waits
+// and failure path.
 constexpr unsigned kPanelPolls = 1u << 20;
-template <int U>
+template <int U, bool MK = false>
 __global__ __launch_bounds__(kThreads) void k_panel_reduce_upd(PanelParams p, int cflag, int G) {
     const int rhs = blockIdx.x % p.k;
     const int g = blockIdx.x / p.k;
@@ -1246,6 +1264,8 @@ __global__ __launch_bounds__(kThreads) void k_panel_reduce_upd(PanelParams p, in
         const double2 r23 = *reinterpret_cast<const double2*>(p.R + e + 2);
         r[u][0] = r01.x; r[u][1] = r01.y; r[u][2] = r23.x; r[u][3] = r23.y;
         ev[u] = (cflag & 3) == 1 ? *reinterpret_cast<const float4*>(p.Ec + e) : make_float4(0.f, 0.f, 0.f, 0.f);
+        unsigned wv = 0;
+        if constexpr (MK) wv = *reinterpret_cast<const unsigned*>(p.W + e);
         const float* src = p.Sslab + e;
 #pragma unroll
         for (int q = 0; q < 4; ++q) s[u][q] = 0.0;
@@ -1263,6 +1283,7 @@ __global__ __launch_bounds__(kThreads) void k_panel_reduce_upd(PanelParams p, in
             const float4 v = *reinterpret_cast<const float4*>(src + c * cstride);
             s[u][0] += (double)v.x; s[u][1] += (double)v.y; s[u][2] += (double)v.z; s[u][3] += (double)v.w;
         }
+        if constexpr (MK) panel_mask4(wv, s[u]);
     }
     // per-group line-search partials, in k_panel_reduce's order
     __shared__ double sr[U][kWaves], sq[U][kWaves];
@@ -1401,6 +1422,19 @@ __global__ __launch_bounds__(kThreads) void k_panel_flush(PanelParams p) {
 }
 __global__ void k_panel_clear_pending(PanelParams p) {
     if (threadIdx.x == 0) p.st->pending = 0;
+}
+
+// reset with a row mask: the caller's full B [k][m] -> Bw = w o B (where the solver and the
+// certificate read B) and Bh = (1 - w) o B (the held-out entries, for the certificate's score)
+__global__ __launch_bounds__(kThreads) void k_panel_mask_b(const double* __restrict__ B,
+                                                           const unsigned char* __restrict__ W, long long n,
+                                                           double* __restrict__ Bw, double* __restrict__ Bh) {
+    for (long long e = (long long)blockIdx.x * kThreads + threadIdx.x; e < n; e += (long long)gridDim.x * kThreads) {
+        const double v = B[e];
+        const bool in = W[e] != 0;
+        Bw[e] = in ? v : 0.0;
+        Bh[e] = in ? 0.0 : v;
+    }
 }
 
 // split an fp64 [k][len] operand into hi/lo bf16 images [k][ld]; optionally R = -B (reset)

@@ -49,6 +49,7 @@ struct bpgl_panel {
     int64_t n_exact = 0;          // carried gradient: exact-gradient iterations since the last reset
     hipEvent_t gap_ev[3] = {};    // bpgl_panel_gap: before product 1, between the products, after product 2
     int64_t gap_ns[2] = {};       // the last call's two products (each with its fold), stats "gap_prod1_ns" / "gap_prod2_ns"
+    bool masked = false;          // bpgl_panel_set_row_mask installed a mask: the MK kernel variants run
     int64_t ldr() const { return m; }
     int64_t ldd() const { return w; }
 };
@@ -57,7 +58,7 @@ namespace {
 
 struct PanelLayout {
     int64_t st, Rh, Rl, Dh, Dl, X, Ax, B, R, diag, rec, Sslab, S, norms, lsp, mu, gamma, err_rhs, cnt, ready, lsdone, Gc,
-        Sh, Ec, At, A1t, gpart, gparts, gcounts, gres, total;
+        Sh, Ec, At, A1t, gpart, gparts, gcounts, gres, W, Bh, ghold, total;
 };
 // bpgl_panel_gap: the chunks of a product's reduction (`stages` 32-deep stages, `tiles` 64-output
 // tiles) -- doubled while the product has fewer than kPgBlocksTarget blocks and a chunk keeps two
@@ -81,7 +82,8 @@ int pgap_prod(bpgl_panel* c, const PanelGapArgs& a, dim3 grid) {
     }
     LAUNCH_CHECK("k_pgap_prod");
     const dim3 fgrid((unsigned)cdiv((int64_t)c->k * (PROD == 1 ? c->m : c->n), kThreads));
-    hipLaunchKernelGGL(k_pgap_fold<PROD>, fgrid, blk, 0, c->stream, a);
+    if (PROD == 1 && c->masked) hipLaunchKernelGGL((k_pgap_fold<1, true>), fgrid, blk, 0, c->stream, a);
+    else hipLaunchKernelGGL((k_pgap_fold<PROD, false>), fgrid, blk, 0, c->stream, a);
     LAUNCH_CHECK("k_pgap_fold");
     return 0;
 }
@@ -125,6 +127,11 @@ PanelLayout panel_layout(const bpgl_panel* c) {
     L.gparts = k.take(8 * (int64_t)kPgPart * pgap_nparts(c) * c->k);
     L.gcounts = k.take(4 * (int64_t)c->k * cdiv(c->n, kThreads));
     L.gres = k.take(8 * (int64_t)kPgRes * c->k);
+    // the row mask (bpgl_panel_set_row_mask), the held-out part of B and the certificate's held-out
+    // partials (one per 256-thread fold block).  Laid out after everything else, as the pieces above were.
+    L.W = k.take(km);
+    L.Bh = k.take(8 * km);
+    L.ghold = k.take(8 * (km / kThreads));
     L.total = k.off;
     return L;
 }
@@ -207,7 +214,10 @@ bool panel_fused_geo(const bpgl_panel* c, int* G, int* U) {
     *U = (int)u;
     return true;
 }
-const void* panel_fused_fn(int U) {
+const void* panel_fused_fn(int U, bool masked) {
+    if (masked)
+        return U == 1 ? (const void*)k_panel_reduce_upd<1, true> : U == 2 ? (const void*)k_panel_reduce_upd<2, true>
+                                                                        : (const void*)k_panel_reduce_upd<4, true>;
     return U == 1 ? (const void*)k_panel_reduce_upd<1> : U == 2 ? (const void*)k_panel_reduce_upd<2>
                                                               : (const void*)k_panel_reduce_upd<4>;
 }
@@ -215,29 +225,36 @@ int panel_reduce_upd(bpgl_panel* c, int cflag) {
     int G = 0, U = 0;
     (void)panel_fused_geo(c, &G, &U);
     const dim3 grid((unsigned)(c->k * G)), blk(kThreads);
-    if (U == 1) hipLaunchKernelGGL(k_panel_reduce_upd<1>, grid, blk, 0, c->stream, c->p, cflag, G);
+    if (c->masked) {
+        if (U == 1) hipLaunchKernelGGL((k_panel_reduce_upd<1, true>), grid, blk, 0, c->stream, c->p, cflag, G);
+        else if (U == 2) hipLaunchKernelGGL((k_panel_reduce_upd<2, true>), grid, blk, 0, c->stream, c->p, cflag, G);
+        else hipLaunchKernelGGL((k_panel_reduce_upd<4, true>), grid, blk, 0, c->stream, c->p, cflag, G);
+    } else if (U == 1) hipLaunchKernelGGL(k_panel_reduce_upd<1>, grid, blk, 0, c->stream, c->p, cflag, G);
     else if (U == 2) hipLaunchKernelGGL(k_panel_reduce_upd<2>, grid, blk, 0, c->stream, c->p, cflag, G);
     else hipLaunchKernelGGL(k_panel_reduce_upd<4>, grid, blk, 0, c->stream, c->p, cflag, G);
     LAUNCH_CHECK("k_panel_reduce_upd");
     return 0;
 }
 // the fused reduce + update needs its k x G blocks resident together: on the CUs the stream may use
-// (a CU-masked stream from bpgl_stream_create gets fewer), else the two-kernel form runs
+// (a CU-masked stream from bpgl_stream_create gets fewer), else the two-kernel form runs.  The
+// occupancy is that of the variant that will run (masked or not), so bpgl_panel_set_row_mask repeats it.
 void panel_fuse_check(bpgl_panel* c) {
     int G = 0, U = 0, nb = 0;
     c->fuse_ok = 0;
     c->fuse_cus = 0;
     if (!panel_fused_geo(c, &G, &U)) return;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, panel_fused_fn(U), kThreads, 0) != hipSuccess) {
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, panel_fused_fn(U, c->masked), kThreads, 0) != hipSuccess) {
         (void)hipGetLastError();   // the query's own error only
         return;
     }
     c->fuse_cus = usable_cus(c->stream, c->device);
     if ((int64_t)nb * c->fuse_cus >= (int64_t)c->k * G) c->fuse_ok = 1;
 }
+// mode 0 (bpgl_panel_mm) is always the unmasked fold
 int panel_reduce(bpgl_panel* c, double* out, int mode) {
-    hipLaunchKernelGGL(k_panel_reduce, dim3((unsigned)(c->k * cdiv(c->m, kLspRows))), dim3(kThreads), 0, c->stream,
-                       c->p, out, mode);
+    const dim3 grid((unsigned)(c->k * cdiv(c->m, kLspRows)));
+    if (mode && c->masked) hipLaunchKernelGGL(k_panel_reduce<true>, grid, dim3(kThreads), 0, c->stream, c->p, out, mode);
+    else hipLaunchKernelGGL(k_panel_reduce<false>, grid, dim3(kThreads), 0, c->stream, c->p, out, mode);
     LAUNCH_CHECK("k_panel_reduce");
     return 0;
 }
@@ -432,6 +449,7 @@ int bpgl_panel_bind(bpgl_panel* c, const void* A, int64_t lda, void* scratch, in
                            c->stream, p.A, p.lda, c->n, const_cast<__bf16*>(p.A1t));
         LAUNCH_CHECK("k_panel_tile");
     }
+    c->masked = false;   // p.W is null again
     panel_fuse_check(c);
     c->bound = true;
     c->have_diag = false;
@@ -484,7 +502,15 @@ int bpgl_panel_reset(bpgl_panel* c, const double* B, const double* mu, double* e
     HIP_TRY(hipSetDevice(c->device));
     PanelParams& p = c->p;
     const int64_t km = (int64_t)c->k * c->m;
-    HIP_TRY(hipMemcpyAsync(const_cast<double*>(p.B), B, 8 * km, hipMemcpyDeviceToDevice, c->stream));
+    if (c->masked) {   // the stored B is w o B (so R0 = -w o B and A x - B stays masked); (1 - w) o B for the score
+        const PanelLayout L = panel_layout(c);
+        hipLaunchKernelGGL(k_panel_mask_b, dim3((unsigned)std::min<int64_t>(cdiv(km, kThreads), 2048)), dim3(kThreads),
+                           0, c->stream, B, p.W, (long long)km, const_cast<double*>(p.B),
+                           (double*)((char*)p.st + (L.Bh - L.st)));
+        LAUNCH_CHECK("k_panel_mask_b");
+    } else {
+        HIP_TRY(hipMemcpyAsync(const_cast<double*>(p.B), B, 8 * km, hipMemcpyDeviceToDevice, c->stream));
+    }
     HIP_TRY(hipMemcpyAsync(const_cast<double*>(p.mu), mu, 8 * c->k, hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(p.X, 0, 4 * (int64_t)c->k * c->w * c->nblock, c->stream));
     HIP_TRY(hipMemsetAsync(p.Ax, 0, 8 * km * c->nblock, c->stream));
@@ -678,6 +704,21 @@ int bpgl_panel_stat(const bpgl_panel* c, const char* key, int64_t* value) {
 
 const double* bpgl_panel_residual(bpgl_panel* c) { return c ? c->p.R : nullptr; }
 
+int bpgl_panel_set_row_mask(bpgl_panel* c, const uint8_t* mask) {
+    int rc;
+    if ((rc = panel_ready(c))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const PanelLayout L = panel_layout(c);
+    unsigned char* W = (unsigned char*)c->p.st + (L.W - L.st);
+    if (mask) HIP_TRY(hipMemcpyAsync(W, mask, (int64_t)c->k * c->m, hipMemcpyDeviceToDevice, c->stream));
+    c->masked = mask != nullptr;
+    c->p.W = mask ? W : nullptr;
+    c->solver = false;   // B is stored masked and the graphs bake the kernel variant in: a reset must follow
+    drop_graphs(c);
+    panel_fuse_check(c);   // the occupancy of the variant that will run
+    return 0;
+}
+
 int bpgl_panel_gap(bpgl_panel* c, double* G_all, double* R_fresh, uint8_t* keep, double* out) {
     int rc;
     if ((rc = panel_ready(c))) return rc;
@@ -708,6 +749,9 @@ int bpgl_panel_gap(bpgl_panel* c, double* G_all, double* R_fresh, uint8_t* keep,
     a.Rf = R_fresh;
     a.G = G_all;
     a.part = (double*)(s + L.gpart);
+    a.W = c->masked ? c->p.W : nullptr;
+    a.Bh = (const double*)(s + L.Bh);
+    a.hpart = (double*)(s + L.ghold);
     for (auto& e : c->gap_ev)
         if (!e) HIP_TRY(hipEventCreate(&e));
     HIP_TRY(hipEventRecord(c->gap_ev[0], c->stream));
@@ -727,6 +771,11 @@ int bpgl_panel_gap(bpgl_panel* c, double* G_all, double* R_fresh, uint8_t* keep,
     LAUNCH_CHECK("k_pgap_partials");
     hipLaunchKernelGGL(k_pgap_final, dim3((unsigned)c->k), dim3(kThreads), 0, c->stream, parts, nparts, a.mu, res);
     LAUNCH_CHECK("k_pgap_final");
+    if (c->masked) {   // res[k][7], which k_pgap_final left at 0
+        hipLaunchKernelGGL(k_pgap_holdout, dim3((unsigned)c->k), dim3(kThreads), 0, c->stream, a.hpart,
+                           (long long)(c->m / kThreads), res);
+        LAUNCH_CHECK("k_pgap_holdout");
+    }
     if (keep) {
         const int64_t nb = cdiv(c->n, kThreads);
         hipLaunchKernelGGL(k_pgap_screen, dim3((unsigned)nb, (unsigned)c->k), dim3(kThreads), 0, c->stream, a, res, keep,

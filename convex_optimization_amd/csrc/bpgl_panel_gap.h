@@ -21,6 +21,11 @@
 //   k_pgap_final            one block per RHS: folds them in block order -> res[k][0..4], res[k][6]
 //   k_pgap_screen           keep[k][j] and per-block counts
 //   k_pgap_count            one block per RHS: res[k][5] = n_keep
+// With a row mask w (bpgl_panel_set_row_mask; B is then stored as w o B):
+//   k_pgap_fold<1, true>    Rf[k][i] = w_ki (a_i . x_k - b_ki), and per 256-thread block (one RHS: m is a
+//                           multiple of 256) the held-out sum of (1 - w_ki)(a_i . x_k - b_ki)^2 from Bh
+//   k_pgap_holdout          one block per RHS: res[k][7] = those block sums added in block order
+// Product 2 and everything after it then describe the masked problem; the screen keeps the full diag.
 // Every reduction walks its dimension in a fixed order (within a chunk: 32-deep stages in index
 // order, 4 at a time through the MFMA; then the chunks; then wave_sum / wave_max, the waves, the
 // blocks in index order).  No floating-point atomics: two calls on the same state return the same
@@ -45,7 +50,7 @@ constexpr int kPgLdV = kPgK + 2;          // k-wide operand  [rhs][depth]
 constexpr int kPgLdA1 = kPgK + 2;         // product 1's A   [output row][depth]
 constexpr int kPgLdA2 = kPgTile + 16;     // product 2's A   [depth][output column]
 constexpr int kPgBlocksTarget = 512;      // the reduction is split until a product has about this many blocks
-constexpr int kPgRes = 8;                 // res[k]: primal, dual, gap, scale, ||g||_inf, n_keep, drift, 0
+constexpr int kPgRes = 8;                 // res[k]: primal, dual, gap, scale, ||g||_inf, n_keep, drift, held-out SSE (0 without a mask)
 constexpr int kPgPart = 5;                // partials per (block, RHS)
 constexpr int kPgPartBlocks = kThreads;   // at most one partial per thread of k_pgap_final
 
@@ -63,6 +68,10 @@ struct PanelGapArgs {
     double* part;         // [spl][k][len]    a product's chunk partials
     int spl;              // chunks of the product being run
     long long chunk;      // stages per chunk
+    // row mask (null without one): the masked fold of product 1 only
+    const unsigned char* W;   // [k][m]
+    const double* Bh;     // [k][m]           (1 - w) o B
+    double* hpart;        // [k m / 256]      held-out partial of each fold block
 };
 
 // bf16 e of 8 in a 16-byte piece -> fp64 (exact)
@@ -174,17 +183,50 @@ __global__ __launch_bounds__(kThreads) void k_pgap_prod(PanelGapArgs a) {
 }
 
 // one thread per (rhs, output): the chunks in index order; product 1 subtracts B and writes Rf[k][i],
-// product 2 writes G[blk][k][j]
-template <int PROD>
+// product 2 writes G[blk][k][j].  MK (product 1 with a row mask; a.B holds w o B): Rf = 0 at the
+// held-out rows, whose squared errors against Bh go to one partial per block (lanes, waves in order)
+template <int PROD, bool MK = false>
 __global__ __launch_bounds__(kThreads) void k_pgap_fold(PanelGapArgs a) {
+    static_assert(!MK || PROD == 1, "the mask enters product 1 only");
     const long long len = PROD == 1 ? a.m : a.n;
     const long long e = (long long)blockIdx.x * kThreads + threadIdx.x;
-    if (e >= (long long)a.k * len) return;
-    const long long k = e / len, o = e % len;
-    double v = a.part[e];
-    for (int c = 1; c < a.spl; ++c) v += a.part[(long long)c * a.k * len + e];
-    if (PROD == 1) a.Rf[e] = v - a.B[e];
-    else a.G[((o / a.w) * a.k + k) * a.w + o % a.w] = v;
+    if constexpr (MK) {
+        // k m is a multiple of kThreads (m is one of 256), so no thread of a block is out of range
+        double v = a.part[e];
+        for (int c = 1; c < a.spl; ++c) v += a.part[(long long)c * a.k * len + e];
+        const bool in = a.W[e] != 0;
+        a.Rf[e] = in ? v - a.B[e] : 0.0;
+        const double h = in ? 0.0 : v - a.Bh[e];
+        const double hh = wave_sum(h * h);
+        __shared__ double red[kWaves];
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        if (lane == 0) red[wave] = hh;
+        __syncthreads();
+        if (threadIdx.x == 0) a.hpart[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+    } else {
+        if (e >= (long long)a.k * len) return;
+        const long long k = e / len, o = e % len;
+        double v = a.part[e];
+        for (int c = 1; c < a.spl; ++c) v += a.part[(long long)c * a.k * len + e];
+        if (PROD == 1) a.Rf[e] = v - a.B[e];
+        else a.G[((o / a.w) * a.k + k) * a.w + o % a.w] = v;
+    }
+}
+
+// one block per RHS: res[k][7] = the held-out partials of its nb fold blocks, thread q taking blocks
+// q, q + kThreads, ... in order and thread 0 adding the threads' sums in thread order
+__global__ __launch_bounds__(kThreads) void k_pgap_holdout(const double* __restrict__ hpart, long long nb,
+                                                           double* __restrict__ res_all) {
+    const int k = blockIdx.x;
+    double s = 0.0;
+    for (long long q = threadIdx.x; q < nb; q += kThreads) s += hpart[(long long)k * nb + q];
+    __shared__ double red[kThreads];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double tot = 0.0;
+    for (int q = 0; q < kThreads; ++q) tot += red[q];
+    res_all[(long long)k * kPgRes + 7] = tot;
 }
 
 // grid (nparts, k); parts[k][nparts][kPgPart]

@@ -29,7 +29,9 @@ runs the forms follow different trajectories to the same fixed point: x within
 
 ``PanelLasso.duality_gap`` certifies the stored fp32 x of every right-hand side (fp64 products on
 the bf16 A), and ``lasso_path`` runs one b against a grid of mu as one panel
-with that certificate as its stopping rule.
+with that certificate as its stopping rule.  ``PanelLasso.set_row_mask`` gives every right-hand side
+0/1 row weights, and ``lasso_cv`` uses them to run K-fold cross-validation over a grid of mu as one
+panel (K folds x J values of mu = K J columns on one bound A).
 
 All compute goes through libbpgl.so (bpgl_panel_* in include/bpgl.h).
 """
@@ -64,6 +66,7 @@ _PANEL_SIGS = {
     "bpgl_panel_stat": (ctypes.c_int, [_p, ctypes.c_char_p, ctypes.POINTER(_i64)]),
     "bpgl_panel_residual": (_p, [_p]),
     "bpgl_panel_gap": (ctypes.c_int, [_p, _p, _p, _p, ctypes.POINTER(ctypes.c_double)]),
+    "bpgl_panel_set_row_mask": (ctypes.c_int, [_p, _p]),
 }
 N._SIGS.update(_PANEL_SIGS)
 
@@ -191,6 +194,22 @@ class PanelLasso:
             N.check(_lib().bpgl_panel_reset(self._ctx, N.ptr(self._Bt), N.ptr(self._mu), N.ptr(self._err_iter),
                                             int(record_len), int(bool(use_graph))), "bpgl_panel_reset")
 
+    def set_row_mask(self, mask):
+        """0/1 row weights per right-hand side: ``mask`` (m, k) bool / uint8 array or tensor, nonzero =
+        the row is in that column's objective, zero = held out; None clears it.  A ``solver_reset``
+        (with the full B) must follow.  The solver then minimises 1/2 ||w o (A x - b)||^2 + mu ||x||_1
+        per column, ``residual_device`` is the masked residual and ``duality_gap`` certifies the masked
+        problems and reports each column's held-out sum of squares (include/bpgl.h)."""
+        with self._on_stream():
+            if mask is None:
+                self._mask = None
+            else:
+                t = mask if isinstance(mask, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(mask))
+                if tuple(t.shape) != (self.MAT_HEIGHT, self.nrhs):
+                    raise ValueError(f"mask must be (m, k) = ({self.MAT_HEIGHT}, {self.nrhs}), got {tuple(t.shape)}")
+                self._mask = (t.to(self.device) != 0).to(torch.uint8).t().contiguous()   # [k][m]
+            N.check(_lib().bpgl_panel_set_row_mask(self._ctx, N.ptr(self._mask)), "bpgl_panel_set_row_mask")
+
     def solver_step(self, n_iter):
         with self._on_stream():
             N.check(_lib().bpgl_panel_step(self._ctx, int(n_iter)), "bpgl_panel_step")
@@ -250,6 +269,8 @@ class PanelLasso:
         (k,) numpy arrays primal, dual, gap, scale, gnorm_inf, n_keep (int64), drift, and the device
         tensors g (k, n) fp64 = A^T r, r (k, m) fp64 = A x - b recomputed from x, keep (k, n) bool
         (None when ``screen`` is false; n_keep is then n).  drift is max |solver residual - r| per RHS.
+        Also holdout_sse (k,): with a row mask the sum of squared errors over each column's held-out
+        rows (everything else then describes the masked problem), zero without one.
         Read-only for the solve and bitwise repeatable.  The tensors are views of buffers the next call
         overwrites (g is a copy when there is more than one feature block)."""
         k, n, m = self.nrhs, self.MAT_WIDTH_ALL, self.MAT_HEIGHT
@@ -265,6 +286,7 @@ class PanelLasso:
         out = np.array(self._gap_out, dtype=np.float64).reshape(k, 8)
         res = {key: out[:, i].copy() for i, key in enumerate(self.GAP_KEYS)}
         res["n_keep"] = res["n_keep"].astype(np.int64)
+        res["holdout_sse"] = out[:, 7].copy()
         res["g"] = self._gap_g.permute(1, 0, 2).reshape(k, n)
         res["r"] = self._gap_r
         res["keep"] = self._gap_keep.view(torch.bool) if screen else None
@@ -308,6 +330,27 @@ def pad_mus(mus):
     return np.concatenate([mus, np.full(k - mus.size, mus.max())]), int(mus.size)
 
 
+def _check_loop(pl, target, ITER_MAX, check_every):
+    """The drivers' loop on a freshly reset ``pl``: ``check_every`` iterations, then a certificate, until
+    every column has gap <= target (a scalar or one per column) or ITER_MAX iterations have run.
+    Returns (iterations run, the last certificate, per column the iteration of the first check at
+    which it met its target, else -1)."""
+    first = np.full(pl.nrhs, -1, dtype=np.int64)
+    t, cert = 0, None
+    while t < int(ITER_MAX):
+        step = min(int(check_every), int(ITER_MAX) - t)
+        pl.solver_step(step)
+        t += step
+        cert = pl.duality_gap(screen=True)
+        ok = cert["gap"] <= target
+        first[ok & (first < 0)] = t
+        if ok.all():
+            break
+    if cert is None:
+        cert = pl.duality_gap(screen=True)
+    return t, cert, first
+
+
 def lasso_path(A, b, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_BOUND=1e-4, ITER_MAX=4096,
                check_every=PATH_CHECK_EVERY, device=None):
     """A regularization path as ONE panel: min 1/2 ||A x - b||^2 + mu ||x||_1 for every mu of a grid,
@@ -348,21 +391,88 @@ def lasso_path(A, b, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_BOUND=1e-4
         grid, _ = pad_mus(mu_grid(mu_max, n_given, hi, lo))
     pl.solver_reset(B, grid)
     target = float(GAP_BOUND) * 0.5 * float(b @ b)
-    first = np.full(k, -1, dtype=np.int64)
-    t, cert = 0, None
-    while t < int(ITER_MAX):
-        step = min(int(check_every), int(ITER_MAX) - t)
-        pl.solver_step(step)
-        t += step
-        cert = pl.duality_gap(screen=True)
-        ok = cert["gap"] <= target
-        first[ok & (first < 0)] = t
-        if ok.all():
-            break
-    if cert is None:
-        cert = pl.duality_gap(screen=True)
+    t, cert, first = _check_loop(pl, target, ITER_MAX, check_every)
     out = dict(x=pl.solver_x()[:, :n_given], mus=grid[:n_given].copy(), mu_max=mu_max, iters=t,
                reached=(cert["gap"] <= target)[:n_given], first_reached=first[:n_given])
     for key in PanelLasso.GAP_KEYS:
         out[key] = cert[key][:n_given]
+    return out
+
+
+def lasso_cv(A, b, n_folds=8, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_BOUND=1e-4, ITER_MAX=4096,
+             check_every=PATH_CHECK_EVERY, seed=0, masks=None, refit=True, return_x=False, device=None):
+    """K-fold cross-validation over a grid of mu as ONE panel on one bound A: column c = f * n_mus + j
+    solves fold f (the rows of ``masks[f]``) at ``mus[j]``, min 1/2 ||w_f o (A x - b)||^2 + mu_j ||x||_1,
+    through ``PanelLasso.set_row_mask``.  n_folds * n_mus <= 128 and n_folds >= 2 (ValueError
+    otherwise); the panel is padded to the next width (16, 32, 64, 128) with copies of column 0, which
+    are dropped from every output.
+
+    ``masks``: (n_folds, m) 0/1, 0 = held out (default ``cpu_calculation.kfold_masks(m, n_folds, seed)``;
+    when given, n_folds is its row count).  One grid serves all folds: ``mus``, or with ``mus=None``
+    ``mu_grid(mu_max, n_mus, hi, lo)`` with mu_max = ||A^T b||_inf of the full data, read off an unmasked
+    certificate at x = 0 as ``lasso_path`` does.
+
+    The loop is ``lasso_path``'s: ``check_every`` iterations, then a certificate; it stops when every
+    column has gap <= GAP_BOUND * 1/2 ||w_f o b||^2, or after ITER_MAX iterations.
+
+    Returns a dict: mus; mse (n_folds, n_mus) = held-out sum of squares / held-out count; mean_mse and
+    se_mse (n_mus,), the mean over folds and its standard error; best = argmin mean_mse; best_1se = the
+    index of the largest mu whose mean_mse is <= the minimum + its standard error; iters; reached, gap
+    and n_keep (n_folds, n_mus) from the last certificate; masks.  ``return_x``: also x_folds
+    (n, n_folds, n_mus).  ``refit``: the mask is cleared on the SAME context (A stays bound) and the
+    full-data path on the grid is solved by the same loop, as ``lasso_path`` pads and stops it: x
+    (n, n_mus), refit_gap (n_mus,) and refit_iters."""
+    from .cpu_calculation import kfold_masks, mu_grid
+    if int(check_every) <= 0:
+        raise ValueError("check_every must be > 0")
+    b = np.asarray(b.detach().cpu() if isinstance(b, torch.Tensor) else b, dtype=np.float64).reshape(-1)
+    m = b.size
+    if masks is not None:
+        masks = (np.asarray(masks.detach().cpu() if isinstance(masks, torch.Tensor) else masks) != 0).astype(np.uint8)
+        if masks.ndim != 2 or masks.shape[1] != m:
+            raise ValueError(f"masks must be (n_folds, m = {m})")
+        n_folds = masks.shape[0]
+    n_folds = int(n_folds)
+    if n_folds < 2:
+        raise ValueError(f"lasso_cv needs n_folds >= 2 (got {n_folds})")
+    if mus is not None:
+        mus = np.asarray(mus, dtype=np.float64).reshape(-1).copy()
+        n_mus = mus.size
+    n_mus = int(n_mus)
+    ncol = n_folds * n_mus
+    if n_mus < 1 or ncol > PANEL_NRHS[-1]:
+        raise ValueError(f"lasso_cv takes n_folds * n_mus between 2 and {PANEL_NRHS[-1]} (got {n_folds} x {n_mus})")
+    if masks is None:
+        masks = kfold_masks(m, n_folds, seed)
+    k = next(v for v in PANEL_NRHS if v >= ncol)
+    pl = PanelLasso(A, Block, nrhs=k, device=device)
+    B = np.repeat(b[:, None], k, axis=1)
+    if mus is None:
+        pl.solver_reset(B, 1.0)
+        mus = mu_grid(float(pl.duality_gap(screen=False)["gnorm_inf"][0]), n_mus, hi, lo)
+    cols = np.concatenate([np.arange(ncol), np.zeros(k - ncol, dtype=np.int64)])   # the pad: copies of column 0
+    fold, jmu = cols // n_mus, cols % n_mus
+    pl.set_row_mask(masks[fold].T)
+    pl.solver_reset(B, mus[jmu])
+    bb = np.array([float((masks[f] * b) @ (masks[f] * b)) for f in range(n_folds)])
+    t, cert, _ = _check_loop(pl, float(GAP_BOUND) * 0.5 * bb[fold], ITER_MAX, check_every)
+    shape = (n_folds, n_mus)
+    count = (masks == 0).sum(axis=1).astype(np.float64)
+    mse = cert["holdout_sse"][:ncol].reshape(shape) / count[:, None]
+    mean_mse = mse.mean(axis=0)
+    se_mse = mse.std(axis=0, ddof=1) / np.sqrt(n_folds)
+    best = int(np.argmin(mean_mse))
+    within = np.flatnonzero(mean_mse <= mean_mse[best] + se_mse[best])
+    out = dict(mus=mus.copy(), mse=mse, mean_mse=mean_mse, se_mse=se_mse, best=best,
+               best_1se=int(within[np.argmax(mus[within])]), iters=t,
+               reached=(cert["gap"] <= float(GAP_BOUND) * 0.5 * bb[fold])[:ncol].reshape(shape),
+               gap=cert["gap"][:ncol].reshape(shape), n_keep=cert["n_keep"][:ncol].reshape(shape), masks=masks)
+    if return_x:
+        out["x_folds"] = pl.solver_x()[:, :ncol].reshape(-1, n_folds, n_mus)
+    if refit:
+        grid = np.concatenate([mus, np.full(k - n_mus, mus.max())])   # pad_mus' layout at this panel's width
+        pl.set_row_mask(None)
+        pl.solver_reset(B, grid)
+        rt, rcert, _ = _check_loop(pl, float(GAP_BOUND) * 0.5 * float(b @ b), ITER_MAX, check_every)
+        out.update(x=pl.solver_x()[:, :n_mus], refit_gap=rcert["gap"][:n_mus], refit_iters=rt)
     return out
