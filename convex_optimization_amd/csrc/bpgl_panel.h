@@ -75,8 +75,8 @@ struct PanelState {
 struct PanelParams {
     const __bf16* A;    // [m][lda]   block b at column offset b * w
     long long lda;
-    const __bf16* At;   // pass 2's copy of A in 256 x 64 tiles, [n / 64][m / 256][256][64] (kPanelTiled2)
-    const __bf16* A1t;  // pass 1's copy of A in 64 x 256 tiles, [m / 64][n / 256][64][256] (kPanelTiled1)
+    const __bf16* At;   // pass 2's copy of A in 256 x 64 tiles, [n / 64][m / 256][256][64] (panel_a2_piece)
+    const __bf16* A1t;  // pass 1's copy of A in 64 x 256 tiles, [m / 64][n / 256][64][256] (panel_a1_piece)
     long long m, w;
     int nblock, k;
     int kchunks;        // pass-2 split of the block's w columns
@@ -122,11 +122,17 @@ __device__ __forceinline__ void panel_mask4(unsigned wv, double (&s)[4]) {
 
 constexpr int kLspRows = 1024;    // rows per line-search partial
 
-// Diagnostic builds only (tools/panel_diag.sh; never the shipped library): bit 0 drops the
-// A-side LDS-DMA pieces after the prologue, bit 1 the RHS-side ones, bits 2 / 3 half / all of the
-// lo operand pieces (panel_op_piece) -- wrong results, used to split a pass's time into MFMA + LDS
-// and each stream's share.  (Round 3's bits 4-6, the lo MFMAs dropped, on e4m3 and on 32x32x16,
-// went with the lo8 and mfma32 forms in rounds 4-5.)
+// Diagnostic, timing-only builds (tools/panel_diag.sh; never the shipped library; results wrong), used
+// to split a pass's time into MFMA + LDS, each stream's share and the epilogue.  Bits 0, 1 and 3 mean
+// one thing in the mainloop and another in the pass-1 shrink epilogue:
+//   bit  mainloop (PanelStages::piece, panel_op_piece)           pass-1 epilogue (register form)
+//   0    no A-side LDS-DMA pieces after the prologue            no carried-G store
+//   1    no RHS-side pieces after the prologue                  no D' (hi) store
+//   2    every other lo operand piece dropped                   --
+//   3    every lo operand piece dropped                         no epilogue loop at all (the products
+//                                                               are only kept alive)
+// (Round 3's bits 4-6, the lo MFMAs dropped, on e4m3 and on 32x32x16, went with the lo8 and mfma32
+// forms in rounds 4-5.)
 #ifndef BPGL_PANEL_DIAG
 #define BPGL_PANEL_DIAG 0
 #endif
@@ -203,13 +209,9 @@ __device__ __forceinline__ void panel_op_piece(int q, const __bf16* __restrict__
     if ((BPGL_PANEL_DIAG & 8) && NS == 2 && pc * 8 >= G::K) return;
     glds16o((hl ? lo : hi) + (long long)rhs * ld + ks + 8 * c, obuf + pc * 1024);
 }
-// pass-1 A stage: rows ks..ks+63 of A, columns col0..col0+255 -> [64][512 B] (a piece = 2 rows).
-// kPanelTiled1 (BPGL_PANEL_T1): from p.A1t, where the stage's 64 x 256 tile is one contiguous 32 KiB
-// ([m / 64][n / 256][64][256]; `lda` is then n / 256)
-#ifndef BPGL_PANEL_T1
-#define BPGL_PANEL_T1 1
-#endif
-constexpr bool kPanelTiled1 = BPGL_PANEL_T1 != 0;
+// pass-1 A stage: rows ks..ks+63 of A, columns col0..col0+255 -> [64][512 B] (a piece = 2 rows), from
+// p.A1t, where the stage's 64 x 256 tile is one contiguous 32 KiB ([m / 64][n / 256][64][256]; `lda` is
+// n / 256, the tiles per row band)
 template <int NT>
 __device__ __forceinline__ void panel_a1_piece(int q, const __bf16* __restrict__ A, long long lda, long long ks,
                                                long long col0, char* abuf, int wave, int lane) {
@@ -217,22 +219,15 @@ __device__ __forceinline__ void panel_a1_piece(int q, const __bf16* __restrict__
     const int pc = q * G::NW + wave;
     const int row = pc * 2 + (lane >> 5);
     const int c = swz512(row, lane & 31);
-    if constexpr (kPanelTiled1)
-        glds16a(A + (((ks >> 6) * lda + (col0 >> 8)) << 14) + row * 256 + 8 * c, abuf + pc * 1024);
-    else
-        glds16a(A + (ks + row) * lda + col0 + 8 * c, abuf + pc * 1024);
+    glds16a(A + (((ks >> 6) * lda + (col0 >> 8)) << 14) + row * 256 + 8 * c, abuf + pc * 1024);
 }
-// pass-2 A stage: rows r0..r0+255 of A, columns ks..ks+63 -> [256][128 B] (a piece = 8 rows).
-// kPanelTiled2 (BPGL_PANEL_T2, default 1): from p.At, where the stage's 256 x 64 tile is one contiguous
-// 32 KiB, the tiles stage-major ([n / 64][m / 256][256][64]; `lda` is then m / 256, the tiles per column
-// strip): the 32 row bands of a column chunk read one contiguous 1 MiB per stage, as pass 1's blocks read
-// one 8 MiB window.  Measured against 128 B from each of 256 rows 128 KiB apart (untiled) and against the
-// tiles band-major (each block streaming its own 4 MiB, 256 streams 4 MiB apart): pass 2 184.4 -> 170.4
-// µs, configs[4] 2583 -> 2670 it/s (round 5: profiles/r05/panel_tiles, profiles/r05/layout)
-#ifndef BPGL_PANEL_T2
-#define BPGL_PANEL_T2 1
-#endif
-constexpr bool kPanelTiled2 = BPGL_PANEL_T2 != 0;
+// pass-2 A stage: rows r0..r0+255 of A, columns ks..ks+63 -> [256][128 B] (a piece = 8 rows), from p.At,
+// where the stage's 256 x 64 tile is one contiguous 32 KiB, the tiles stage-major ([n / 64][m / 256][256][64];
+// `lda` is m / 256, the tiles per column strip): the 32 row bands of a column chunk read one contiguous
+// 1 MiB per stage, as pass 1's blocks read one 8 MiB window.  Measured against 128 B from each of 256 rows
+// 128 KiB apart (the untiled A, a form removed since) and against the tiles band-major (each block
+// streaming its own 4 MiB, 256 streams 4 MiB apart): pass 2 184.4 -> 170.4 µs, configs[4] 2583 -> 2670 it/s
+// (round 5: profiles/r05/panel_tiles, profiles/r05/layout)
 template <int NT>
 __device__ __forceinline__ void panel_a2_piece(int q, const __bf16* __restrict__ A, long long lda, long long r0,
                                                long long ks, char* abuf, int wave, int lane) {
@@ -240,10 +235,7 @@ __device__ __forceinline__ void panel_a2_piece(int q, const __bf16* __restrict__
     const int pc = q * G::NW + wave;
     const int row = pc * 8 + (lane >> 3);
     const int c = swz128(row, lane & 7);
-    if constexpr (kPanelTiled2)
-        glds16a(A + (((ks >> 6) * lda + (r0 >> 8)) << 14) + row * 64 + 8 * c, abuf + pc * 1024);
-    else
-        glds16a(A + (r0 + row) * lda + ks + 8 * c, abuf + pc * 1024);
+    glds16a(A + (((ks >> 6) * lda + (r0 >> 8)) << 14) + row * 64 + 8 * c, abuf + pc * 1024);
 }
 // a tiled copy of A: tile (band, ct) = rows TR band .., columns TC ct .. as one contiguous TR x TC block
 // (32 KiB); a thread copies 128 B of it.  grid = (m / TR) x (n / TC).  Tiles in the order their pass's stages
@@ -294,11 +286,22 @@ __device__ __forceinline__ bf16x8 panel_afrag1(const char* abuf, int j0, int h, 
 // `a_row0`/`a_col0`: PASS 1 -> (first A row of K, first column of the tile); PASS 2 -> (first row, first column of K).
 // ILV 0: a stage's LDS-DMA pieces are issued together after the barrier; ILV 1: they
 // are spread over the stage's MFMA groups (one scheduling group each).  NS: operand pieces.
+// ILV 2 is the software-pipelined form of the same GEMM.  The stage barrier sits before a stage's LAST
+// MFMA group: the fragments of the next stage's first group are read behind that group's MFMAs, and
+// every group's fragments are read one group ahead.  Buffer reuse is unchanged (a stage's buffers are
+// refilled only after the barrier that follows all of its reads); all LDS-DMA pieces of a stage are
+// issued before its barrier, spread over the first G - 1 groups.
+// The forms share the accumulator zeroing, the stage buffers carved from `smem`, a stage's LDS-DMA pieces
+// (`piece`, with the BPGL_PANEL_DIAG gates) and the fragment reads, and are the branches of this one
+// function on purpose: with a loop form behind a call of its own -- or with the ILV 0 / 1 loop's A
+// fragments read through `read_a` instead of in place -- hipcc does the pass kernels' integer address
+// arithmetic differently (other v_add / v_or / v_lshl mixes, a VGPR more in k_panel_pass2<4, 1, 1>); as
+// written every pass kernel is instruction for instruction what the separate mainloops compiled to.
 template <int NT, int PASS, int ILV, int NS>
-__device__ __forceinline__ void panel_mainloop(char* smem, const __bf16* __restrict__ A, long long lda,
-                                               long long a_row0, long long a_col0, const __bf16* __restrict__ bh,
-                                               const __bf16* __restrict__ bl, long long ldb, long long b_k0,
-                                               int nsteps, f32x4 (&acc)[4][PanelGeo<NT, 2>::NTW]) {
+__device__ __forceinline__ void panel_gemm(char* smem, const __bf16* __restrict__ A, long long lda,
+                                           long long a_row0, long long a_col0, const __bf16* __restrict__ bh,
+                                           const __bf16* __restrict__ bl, long long ldb, long long b_k0,
+                                           int nsteps, f32x4 (&acc)[4][PanelGeo<NT, 2>::NTW]) {
     using G = PanelGeo<NT, NS>;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -311,7 +314,7 @@ __device__ __forceinline__ void panel_mainloop(char* smem, const __bf16* __restr
         for (int nt = 0; nt < G::NTW; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     // piece i of stage (so, sa): i < LO -> k-wide piece, else A piece i - LO (this order is what
-    // the counted wait below assumes: the youngest LA operations are A pieces)
+    // the counted waits below assume: the youngest LA operations are A pieces)
     auto piece = [&](int i, int so, int bo, int sa, int ba) {
         if ((BPGL_PANEL_DIAG & 1) && i >= G::LO && (so | sa) != 0) return;
         if ((BPGL_PANEL_DIAG & 2) && i < G::LO && (so | sa) != 0) return;
@@ -326,166 +329,127 @@ __device__ __forceinline__ void panel_mainloop(char* smem, const __bf16* __restr
                                     abufs + ba * kPanelAStage, wave, lane);
         }
     };
-    auto issue_a = [&](int s, int buf) {
-#pragma unroll
-        for (int i = G::LO; i < G::LO + G::LA; ++i) piece(i, 0, 0, s, buf);
-    };
-    auto issue_o = [&](int s, int buf) {
-#pragma unroll
-        for (int i = 0; i < G::LO; ++i) piece(i, s, buf, 0, 0);
-    };
-    constexpr int NP = G::LO + G::LA;
-    constexpr int NG = 2 * G::NTW;                 // MFMA groups per stage
-    constexpr int PPG = (NP + NG - 1) / NG;         // pieces per group (ILV)
-    // prologue: op(0), A(0), A(1) -- the loop's counted wait assumes exactly this issue order
-    issue_o(0, 0);
-    issue_a(0, 0);
-    issue_a(nsteps > 1 ? 1 : 0, 1);
-    int abuf = 0;
-    for (int s = 0; s < nsteps; ++s) {
-        // everything but A(s+1) has landed (op(s), A(s)); every wave is past stage s-1's reads
-        wait_vm_barrier<G::LA>();
-        const int so = s + 1 < nsteps ? s + 1 : nsteps - 1;     // clamped tail: loads into unread buffers
-        const int sa = s + 2 < nsteps ? s + 2 : nsteps - 1;
-        const int bo = (s + 1) & 1, ba = abuf == 0 ? 2 : abuf - 1;   // (s + 2) % 3
-        if (!ILV) {
-#pragma unroll
-            for (int i = 0; i < NP; ++i) piece(i, so, bo, sa, ba);
-        }
-        const char* ab = abufs + abuf * kPanelAStage;
-        const char* ob = obufs + (s & 1) * G::OStage;
-        static_for<0, 2>([&](auto hc) {
-            constexpr int h = decltype(hc)::value;
-            bf16x8 af[4];
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
-                af[mt] = PASS == 1 ? panel_afrag1(ab, wm * 64 + mt * 16, h, lane)
-                                   : panel_afrag2(ab, wm * 64 + mt * 16 + (lane & 15), h, lane);
-            static_for<0, G::NTW>([&](auto ntc) {
-                constexpr int nt = decltype(ntc)::value;
-                constexpr int grp = h * G::NTW + nt;
-                constexpr int p0 = grp * PPG < NP ? grp * PPG : NP;
-                constexpr int p1 = (grp + 1) * PPG < NP ? (grp + 1) * PPG : NP;
-                if constexpr (ILV) {
-                    static_for<p0, p1>([&](auto ic) { piece(decltype(ic)::value, so, bo, sa, ba); });
-                }
-                const int rhs = (wn * G::NTW + nt) * 16 + (lane & 15);
-                const bf16x8 b_hi = panel_bfrag(ob, rhs, h, lane);
-                bf16x8 b_lo;
-                if constexpr (NS == 2) b_lo = panel_bfrag(ob, G::K + rhs, h, lane);
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt) {
-                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[mt], b_hi, acc[mt][nt], 0, 0, 0);
-                    if constexpr (NS == 2)
-                        acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[mt], b_lo, acc[mt][nt], 0, 0, 0);
-                }
-                if constexpr (ILV) {
-                    if constexpr (p1 > p0) __builtin_amdgcn_sched_group_barrier(0x20, p1 - p0, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x8, 4 * NS, 0);
-                }
-            });
-        });
-        abuf = abuf == 2 ? 0 : abuf + 1;
-    }
-    wait_vm_barrier<0>();   // the clamped tail loads have landed; LDS free for the epilogue
-}
-
-// Software-pipelined form of the same GEMM (interleave knob 2).  The stage barrier sits
-// before a stage's LAST MFMA group: the fragments of the next stage's first group are read
-// behind that group's MFMAs, and every group's fragments are read one group ahead.  Buffer
-// reuse is unchanged (a stage's buffers are refilled only after the barrier that follows
-// all of its reads); all LDS-DMA pieces of a stage are issued before its barrier, spread
-// over the first G - 1 groups.
-template <int NT, int PASS, int NS>
-__device__ __forceinline__ void panel_mainloop_pipe(char* smem, const __bf16* __restrict__ A, long long lda,
-                                                    long long a_row0, long long a_col0,
-                                                    const __bf16* __restrict__ bh, const __bf16* __restrict__ bl,
-                                                    long long ldb, long long b_k0, int nsteps,
-                                                    f32x4 (&acc)[4][PanelGeo<NT, 2>::NTW]) {
-    using G = PanelGeo<NT, NS>;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wm = wave & 3, wn = wave >> 2;
-    char* abufs = smem;
-    char* obufs = smem + kPanelNA * kPanelAStage;
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < G::NTW; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    auto piece = [&](int i, int so, int bo, int sa, int ba) {
-        if ((BPGL_PANEL_DIAG & 1) && i >= G::LO && (so | sa) != 0) return;
-        if ((BPGL_PANEL_DIAG & 2) && i < G::LO && (so | sa) != 0) return;
-        if (i < G::LO) {
-            panel_op_piece<NT, NS>(i, bh, bl, ldb, b_k0 + (long long)so * kPanelK, obufs + bo * G::OStage,
-                                        wave, lane);
-        } else if (PASS == 1) {
-            panel_a1_piece<NT>(i - G::LO, A, lda, a_row0 + (long long)sa * kPanelK, a_col0,
-                                    abufs + ba * kPanelAStage, wave, lane);
-        } else {
-            panel_a2_piece<NT>(i - G::LO, A, lda, a_row0, a_col0 + (long long)sa * kPanelK,
-                                    abufs + ba * kPanelAStage, wave, lane);
-        }
-    };
-    constexpr int NP = G::LO + G::LA;
-    constexpr int NG = 2 * G::NTW;                                  // MFMA groups per stage (h, nt)
-    constexpr int NGI = NG > 1 ? NG - 1 : 1;                        // groups that carry LDS-DMA pieces
-    constexpr int PPG = (NP + NGI - 1) / NGI;
+    // the wave's 4 A fragments of K half h from the stage image `ab`
     auto read_a = [&](const char* ab, int h, bf16x8 (&af)[4]) {
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt)
             af[mt] = PASS == 1 ? panel_afrag1(ab, wm * 64 + mt * 16, h, lane)
                                : panel_afrag2(ab, wm * 64 + mt * 16 + (lane & 15), h, lane);
     };
+    // the B fragments (hi, and lo when NS = 2) of the wave's N-tile nt, K half h, from the stage image `ob`
     auto read_b = [&](const char* ob, int h, int nt, bf16x8& bhi, bf16x8& blo) {
         const int rhs = (wn * G::NTW + nt) * 16 + (lane & 15);
         bhi = panel_bfrag(ob, rhs, h, lane);
         if constexpr (NS == 2) blo = panel_bfrag(ob, G::K + rhs, h, lane);
     };
-
-    // prologue: op(0), A(0), A(1), then stage 0 landed and group 0's fragments read
-    for (int i = 0; i < G::LO; ++i) piece(i, 0, 0, 0, 0);
-    for (int i = G::LO; i < NP; ++i) piece(i, 0, 0, 0, 0);
-    for (int i = G::LO; i < NP; ++i) piece(i, 0, 0, nsteps > 1 ? 1 : 0, 1);
-    wait_vm_barrier<G::LA>();
-    bf16x8 af[2][4];
-    bf16x8 bfr[2][2];
-    read_a(abufs, 0, af[0]);
-    read_b(obufs, 0, 0, bfr[0][0], bfr[0][1]);
-    int abuf = 0;
-    for (int s = 0; s < nsteps; ++s) {
-        const int so = s + 1 < nsteps ? s + 1 : nsteps - 1;     // clamped tail: loads into unread buffers
-        const int sa = s + 2 < nsteps ? s + 2 : nsteps - 1;
-        const int bo = (s + 1) & 1, ba = abuf == 0 ? 2 : abuf - 1;   // (s + 2) % 3
-        const int abuf_next = abuf == 2 ? 0 : abuf + 1;
-        const char* ab = abufs + abuf * kPanelAStage;
-        const char* ob = obufs + (s & 1) * G::OStage;
-        static_for<0, NG>([&](auto gc) {
-            constexpr int g = decltype(gc)::value;
-            constexpr int h = g / G::NTW, nt = g % G::NTW;
-            constexpr int cb = g & 1, ca = h & 1;
-            constexpr int p0 = g < NGI ? (g * PPG < NP ? g * PPG : NP) : NP;
-            constexpr int p1 = g < NGI ? ((g + 1) * PPG < NP ? (g + 1) * PPG : NP) : NP;
-            static_for<p0, p1>([&](auto ic) { piece(decltype(ic)::value, so, bo, sa, ba); });
-            if constexpr (g + 1 < NG) {
-                constexpr int h1 = (g + 1) / G::NTW, nt1 = (g + 1) % G::NTW;
-                if constexpr (h1 != h) read_a(ab, h1, af[h1 & 1]);
-                read_b(ob, h1, nt1, bfr[cb ^ 1][0], bfr[cb ^ 1][1]);
-            } else {
-                // stage s + 1 landed (only A(s+2) may be outstanding); stage s's reads retired
-                wait_vm_barrier<G::LA>();
-                const char* abn = abufs + abuf_next * kPanelAStage;
-                const char* obn = obufs + ((s + 1) & 1) * G::OStage;
-                read_a(abn, 0, af[0]);   // the last group runs on af[1] (h = 1)
-                read_b(obn, 0, 0, bfr[cb ^ 1][0], bfr[cb ^ 1][1]);
-            }
+    constexpr int NP = G::LO + G::LA;
+    constexpr int NG = 2 * G::NTW;                 // MFMA groups per stage (h, nt)
+    if constexpr (ILV < 2) {
+        auto issue_a = [&](int s, int buf) {
 #pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-                acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ca][mt], bfr[cb][0], acc[mt][nt], 0, 0, 0);
-                if constexpr (NS == 2)
-                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ca][mt], bfr[cb][1], acc[mt][nt], 0, 0, 0);
+            for (int i = G::LO; i < G::LO + G::LA; ++i) piece(i, 0, 0, s, buf);
+        };
+        auto issue_o = [&](int s, int buf) {
+#pragma unroll
+            for (int i = 0; i < G::LO; ++i) piece(i, s, buf, 0, 0);
+        };
+        constexpr int PPG = (NP + NG - 1) / NG;         // pieces per group (ILV)
+        // prologue: op(0), A(0), A(1) -- the loop's counted wait assumes exactly this issue order
+        issue_o(0, 0);
+        issue_a(0, 0);
+        issue_a(nsteps > 1 ? 1 : 0, 1);
+        int abuf = 0;
+        for (int s = 0; s < nsteps; ++s) {
+            // everything but A(s+1) has landed (op(s), A(s)); every wave is past stage s-1's reads
+            wait_vm_barrier<G::LA>();
+            const int so = s + 1 < nsteps ? s + 1 : nsteps - 1;     // clamped tail: loads into unread buffers
+            const int sa = s + 2 < nsteps ? s + 2 : nsteps - 1;
+            const int bo = (s + 1) & 1, ba = abuf == 0 ? 2 : abuf - 1;   // (s + 2) % 3
+            if (!ILV) {
+#pragma unroll
+                for (int i = 0; i < NP; ++i) piece(i, so, bo, sa, ba);
             }
-        });
-        abuf = abuf_next;
+            const char* ab = abufs + abuf * kPanelAStage;
+            const char* ob = obufs + (s & 1) * G::OStage;
+            static_for<0, 2>([&](auto hc) {
+                constexpr int h = decltype(hc)::value;
+                bf16x8 af[4];   // read_a's loop in place (see above)
+#pragma unroll
+                for (int mt = 0; mt < 4; ++mt)
+                    af[mt] = PASS == 1 ? panel_afrag1(ab, wm * 64 + mt * 16, h, lane)
+                                       : panel_afrag2(ab, wm * 64 + mt * 16 + (lane & 15), h, lane);
+                static_for<0, G::NTW>([&](auto ntc) {
+                    constexpr int nt = decltype(ntc)::value;
+                    constexpr int grp = h * G::NTW + nt;
+                    constexpr int p0 = grp * PPG < NP ? grp * PPG : NP;
+                    constexpr int p1 = (grp + 1) * PPG < NP ? (grp + 1) * PPG : NP;
+                    if constexpr (ILV) {
+                        static_for<p0, p1>([&](auto ic) { piece(decltype(ic)::value, so, bo, sa, ba); });
+                    }
+                    bf16x8 b_hi, b_lo;
+                    read_b(ob, h, nt, b_hi, b_lo);
+#pragma unroll
+                    for (int mt = 0; mt < 4; ++mt) {
+                        acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[mt], b_hi, acc[mt][nt], 0, 0, 0);
+                        if constexpr (NS == 2)
+                            acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[mt], b_lo, acc[mt][nt], 0, 0, 0);
+                    }
+                    if constexpr (ILV) {
+                        if constexpr (p1 > p0) __builtin_amdgcn_sched_group_barrier(0x20, p1 - p0, 0);
+                        __builtin_amdgcn_sched_group_barrier(0x8, 4 * NS, 0);
+                    }
+                });
+            });
+            abuf = abuf == 2 ? 0 : abuf + 1;
+        }
+    } else {
+        constexpr int NGI = NG > 1 ? NG - 1 : 1;                        // groups that carry LDS-DMA pieces
+        constexpr int PPG = (NP + NGI - 1) / NGI;
+        // prologue: op(0), A(0), A(1), then stage 0 landed and group 0's fragments read
+        for (int i = 0; i < G::LO; ++i) piece(i, 0, 0, 0, 0);
+        for (int i = G::LO; i < NP; ++i) piece(i, 0, 0, 0, 0);
+        for (int i = G::LO; i < NP; ++i) piece(i, 0, 0, nsteps > 1 ? 1 : 0, 1);
+        wait_vm_barrier<G::LA>();
+        bf16x8 af[2][4];
+        bf16x8 bfr[2][2];
+        read_a(abufs, 0, af[0]);
+        read_b(obufs, 0, 0, bfr[0][0], bfr[0][1]);
+        int abuf = 0;
+        for (int s = 0; s < nsteps; ++s) {
+            const int so = s + 1 < nsteps ? s + 1 : nsteps - 1;     // clamped tail: loads into unread buffers
+            const int sa = s + 2 < nsteps ? s + 2 : nsteps - 1;
+            const int bo = (s + 1) & 1, ba = abuf == 0 ? 2 : abuf - 1;   // (s + 2) % 3
+            const int abuf_next = abuf == 2 ? 0 : abuf + 1;
+            const char* ab = abufs + abuf * kPanelAStage;
+            const char* ob = obufs + (s & 1) * G::OStage;
+            static_for<0, NG>([&](auto gc) {
+                constexpr int g = decltype(gc)::value;
+                constexpr int h = g / G::NTW, nt = g % G::NTW;
+                constexpr int cb = g & 1, ca = h & 1;
+                constexpr int p0 = g < NGI ? (g * PPG < NP ? g * PPG : NP) : NP;
+                constexpr int p1 = g < NGI ? ((g + 1) * PPG < NP ? (g + 1) * PPG : NP) : NP;
+                static_for<p0, p1>([&](auto ic) { piece(decltype(ic)::value, so, bo, sa, ba); });
+                if constexpr (g + 1 < NG) {
+                    constexpr int h1 = (g + 1) / G::NTW, nt1 = (g + 1) % G::NTW;
+                    if constexpr (h1 != h) read_a(ab, h1, af[h1 & 1]);
+                    read_b(ob, h1, nt1, bfr[cb ^ 1][0], bfr[cb ^ 1][1]);
+                } else {
+                    // stage s + 1 landed (only A(s+2) may be outstanding); stage s's reads retired
+                    wait_vm_barrier<G::LA>();
+                    const char* abn = abufs + abuf_next * kPanelAStage;
+                    const char* obn = obufs + ((s + 1) & 1) * G::OStage;
+                    read_a(abn, 0, af[0]);   // the last group runs on af[1] (h = 1)
+                    read_b(obn, 0, 0, bfr[cb ^ 1][0], bfr[cb ^ 1][1]);
+                }
+#pragma unroll
+                for (int mt = 0; mt < 4; ++mt) {
+                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ca][mt], bfr[cb][0], acc[mt][nt], 0, 0, 0);
+                    if constexpr (NS == 2)
+                        acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ca][mt], bfr[cb][1], acc[mt][nt], 0, 0, 0);
+                }
+            });
+            abuf = abuf_next;
+        }
     }
     wait_vm_barrier<0>();   // the clamped tail loads have landed; LDS free for the epilogue
 }
@@ -525,6 +489,44 @@ __device__ __forceinline__ u32x4 lds_rd128(unsigned addr) {
     return v;
 }
 
+// x += gamma D' on N consecutive elements of one RHS, D' = hq (+ lq when DS = 2) as the MFMA saw it (V: a
+// vector of N bf16).  Returns whether any element can have changed (x + gamma * 0 is x), which the
+// epilogue forms use to leave unchanged columns' stored x alone.  Every place that applies the x update
+// -- both pass-1 epilogue forms when it was deferred, k_panel_update and k_panel_flush -- goes through
+// here, so x is bitwise the same wherever the update runs.
+template <int DS, int N, typename V>
+__device__ __forceinline__ bool panel_apply_x(float (&xs)[N], const V& hq, const V& lq, double g) {
+    bool chg = false;
+#pragma unroll
+    for (int r = 0; r < N; ++r) {
+        double dq = (double)(float)hq[r];
+        if constexpr (DS == 2) dq += (double)(float)lq[r];
+        chg = chg || (dq != 0.0 && g != 0.0);
+        xs[r] = (float)((double)xs[r] + g * dq);
+    }
+    return chg;
+}
+// 8 consecutive x elements ([k][w], unit u) of the block whose x starts at X: the 16-B Dh (+ Dl) loads
+// and the update -- k_panel_update's x half and all of k_panel_flush
+template <int DS>
+__device__ __forceinline__ void panel_x_update8(const PanelParams& p, float* X, unsigned u, unsigned w8) {
+    typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
+    const long long e = 8ll * u;
+    const unsigned rhs = u / w8;
+    const long long de = (long long)rhs * p.ldd + (e - (long long)rhs * p.w);   // operand image index
+    const double g = p.gamma[rhs];
+    const bf16x8v dh = *reinterpret_cast<const bf16x8v*>(p.Dh + de);
+    bf16x8v dl = dh;   // (not read when DS = 1)
+    if constexpr (DS == 2) dl = *reinterpret_cast<const bf16x8v*>(p.Dl + de);
+    float* xp = X + e;
+    float4 x0 = *reinterpret_cast<const float4*>(xp);
+    float4 x1 = *reinterpret_cast<const float4*>(xp + 4);
+    float xs[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+    panel_apply_x<DS>(xs, dh, dl, g);
+    *reinterpret_cast<float4*>(xp) = make_float4(xs[0], xs[1], xs[2], xs[3]);
+    *reinterpret_cast<float4*>(xp + 4) = make_float4(xs[4], xs[5], xs[6], xs[7]);
+}
+
 // one (RHS tile, column group) step of the shrink epilogue: the lane's 4 columns of one RHS -- g from
 // the product (+ the carried G), the prox step, D' in DS bf16 pieces, the norm / error partials
 template <int DS, int GM>
@@ -550,7 +552,7 @@ __device__ __forceinline__ void panel_shrink4(const f32x4& acc, const float (&xs
         sbx += fabs(x + dprime);
         sx += fabs(x);
         const double e = fabs(g - proj(g - x, -mu, mu));
-        err = (e > err || e != e) ? e : err;
+        err = nan_max(err, e);
     }
 }
 // the per-RHS partials of one wave's RHS tile (lanes l, l^16, l^32, l^48 share the RHS) -> nred
@@ -559,8 +561,8 @@ __device__ __forceinline__ void panel_norms_wave(double* nred, int wm, int K, in
     const int lane = threadIdx.x & 63;
     sbx += __shfl_xor(sbx, 16); sbx += __shfl_xor(sbx, 32);
     sx += __shfl_xor(sx, 16);   sx += __shfl_xor(sx, 32);
-    { double o = __shfl_xor(err, 16); err = (o > err || o != o) ? o : err;
-      o = __shfl_xor(err, 32); err = (o > err || o != o) ? o : err; }
+    err = nan_max(err, __shfl_xor(err, 16));
+    err = nan_max(err, __shfl_xor(err, 32));
     if (lane < 16) {
         double* d = nred + ((long long)wm * K + rhs) * 4;
         d[0] = sbx;
@@ -578,15 +580,14 @@ __device__ __forceinline__ void panel_norms_out(const PanelParams& p, const doub
             const double* d = nred + ((long long)q * K + rhs) * 4;
             a += d[0];
             b += d[1];
-            e = (d[2] > e || d[2] != d[2]) ? d[2] : e;
+            e = nan_max(e, d[2]);
         }
         double* dst = p.norms + ((long long)blockIdx.x * p.k + rhs) * 4;
         dst[0] = a; dst[1] = b; dst[2] = e; dst[3] = 0.0;
     }
 }
 
-// BPGL_PANEL_DIAG (timing-only builds, tools/panel_diag.sh; results wrong): bit 0 -- no carried-G
-// store, bit 1 -- no D' store, bit 3 -- no epilogue loop at all (the products are only kept alive)
+// (BPGL_PANEL_DIAG's epilogue bits: see the macro.)
 template <int NTW, int EPI, int DS, int GM = 0, int NW = 0>
 __device__ __forceinline__ void panel_pass1_epilogue(const PanelParams& p, int mb, long long c0, int wm, int wn,
                                                      int T, f32x4 (&acc)[4][NTW], char* smem,
@@ -701,22 +702,14 @@ __device__ __forceinline__ void panel_pass1_epilogue(const PanelParams& p, int m
                 const double rcv[4] = {r01.x, r01.y, r23.x, r23.y};
                 float xs[4] = {x4.x, x4.y, x4.z, x4.w};
                 if (fx) {
-                    bf16x4 hq = dpre[nt & 1][mt], lq;
+                    bf16x4 hq = dpre[nt & 1][mt], lq = hq;   // (lq is not read when DS = 1)
                     if constexpr (DS == 2) {
                         hq = *reinterpret_cast<const bf16x4*>(p.Dh + (long long)rhs * p.ldd + j);
                         lq = *reinterpret_cast<const bf16x4*>(p.Dl + (long long)rhs * p.ldd + j);
                     }
-                    bool chg = false;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        double dq = (double)(float)hq[r];
-                        if constexpr (DS == 2) dq += (double)(float)lq[r];
-                        chg = chg || (dq != 0.0 && gprev != 0.0);
-                        xs[r] = (float)((double)xs[r] + gprev * dq);
-                    }
                     // x + gamma * 0 is x: columns the step left alone (most of a sparse solution's) keep
                     // their stored x, which saves a share of the 32 MiB X write at configs[4]
-                    if (chg)
+                    if (panel_apply_x<DS>(xs, hq, lq, gprev))
                         put(p.X, ((long long)mb * p.k + rhs) * p.w + j, make_float4(xs[0], xs[1], xs[2], xs[3]));
                 }
                 __bf16 dh[4], dl[4];
@@ -802,18 +795,10 @@ __device__ __forceinline__ void panel_pass1_epilogue(const PanelParams& p, int m
             }
             float xs[4] = {xq.x, xq.y, xq.z, xq.w};
             if (fx) {
-                bf16x4 hq = hq1, lq;
+                bf16x4 hq = hq1, lq = hq;   // (lq is not read when DS = 1)
                 if constexpr (DS == 2) hq = *reinterpret_cast<const bf16x4*>(dptr(p.Dh, nt, mt));
                 if constexpr (DS == 2) lq = *reinterpret_cast<const bf16x4*>(dptr(p.Dl, nt, mt));
-                bool chg = false;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    double dq = (double)(float)hq[r];
-                    if constexpr (DS == 2) dq += (double)(float)lq[r];
-                    chg = chg || (dq != 0.0 && gprev != 0.0);
-                    xs[r] = (float)((double)xs[r] + gprev * dq);
-                }
-                if (chg)   // x + gamma * 0 is x: unchanged columns keep their stored x
+                if (panel_apply_x<DS>(xs, hq, lq, gprev))   // unchanged columns keep their stored x
                     put(p.X, ((long long)mb * p.k + rhs) * p.w + j, make_float4(xs[0], xs[1], xs[2], xs[3]));
             }
             __bf16 dh[4], dl[4];
@@ -856,26 +841,14 @@ __global__ __launch_bounds__((PanelGeo<NT, 2>::T)) void k_panel_pass1(PanelParam
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wm = wave & 3, wn = wave >> 2;
     const long long c0 = (long long)blockIdx.x * kPanelRows;             // first column of this block (in block mb)
-    const __bf16* A1 = kPanelTiled1 ? p.A1t : p.A;
-    const long long ld1 = kPanelTiled1 ? (long long)p.nblock * p.w / 256 : p.lda;
+    const long long ld1 = (long long)p.nblock * p.w / 256;   // A1t's tiles per row band
     f32x4 acc[4][G::NTW];
-    if constexpr (GM == 2) {   // carried iteration: U = A^T bf16(V_{t-1}), one bf16 operand
-        if constexpr (ILV >= 2)
-            panel_mainloop_pipe<NT, 1, 1>(smem, A1, ld1, 0, (long long)mb * p.w + c0, p.Sh, p.Sh, p.ldr, 0,
-                                          (int)(p.m / kPanelK), acc);
-        else
-            panel_mainloop<NT, 1, ILV, 1>(smem, A1, ld1, 0, (long long)mb * p.w + c0, p.Sh, p.Sh, p.ldr, 0,
-                                          (int)(p.m / kPanelK), acc);
-        panel_pass1_epilogue<G::NTW, EPI, DS, 2, G::NW>(p, mb, c0, wm, wn, G::T, acc, smem, Gout);
-        return;
-    }
-    if constexpr (ILV >= 2)
-        panel_mainloop_pipe<NT, 1, 2>(smem, A1, ld1, 0, (long long)mb * p.w + c0, p.Rh, p.Rl, p.ldr, 0,
-                                      (int)(p.m / kPanelK), acc);
+    if constexpr (GM == 2)   // carried iteration: U = A^T bf16(V_{t-1}), one bf16 operand
+        panel_gemm<NT, 1, ILV, 1>(smem, p.A1t, ld1, 0, (long long)mb * p.w + c0, p.Sh, p.Sh, p.ldr, 0,
+                                  (int)(p.m / kPanelK), acc);
     else
-        panel_mainloop<NT, 1, ILV, 2>(smem, A1, ld1, 0, (long long)mb * p.w + c0, p.Rh, p.Rl, p.ldr, 0,
-                                      (int)(p.m / kPanelK), acc);
-
+        panel_gemm<NT, 1, ILV, 2>(smem, p.A1t, ld1, 0, (long long)mb * p.w + c0, p.Rh, p.Rl, p.ldr, 0,
+                                  (int)(p.m / kPanelK), acc);
     panel_pass1_epilogue<G::NTW, EPI, DS, GM, G::NW>(p, mb, c0, wm, wn, G::T, acc, smem, Gout);
 }
 
@@ -907,14 +880,8 @@ __global__ __launch_bounds__((PanelGeo<NT, NS>::T)) void k_panel_pass2(PanelPara
     const long long kc = p.w / p.kchunks;
     const long long r0 = (long long)rb * kPanelRows;
     f32x4 acc[4][G::NTW];
-    const __bf16* A2 = kPanelTiled2 ? p.At : p.A;
-    const long long ld2 = kPanelTiled2 ? p.m / 256 : p.lda;
-    if constexpr (ILV >= 2)
-        panel_mainloop_pipe<NT, 2, NS>(smem, A2, ld2, r0, (long long)mb * p.w + chunk * kc, p.Dh, p.Dl, p.ldd,
-                                       chunk * kc, (int)(kc / kPanelK), acc);
-    else
-        panel_mainloop<NT, 2, ILV, NS>(smem, A2, ld2, r0, (long long)mb * p.w + chunk * kc, p.Dh, p.Dl, p.ldd,
-                                       chunk * kc, (int)(kc / kPanelK), acc);
+    panel_gemm<NT, 2, ILV, NS>(smem, p.At, p.m / 256, r0, (long long)mb * p.w + chunk * kc, p.Dh, p.Dl, p.ldd,
+                               chunk * kc, (int)(kc / kPanelK), acc);   // lda: At's tiles per column strip
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
@@ -945,8 +912,69 @@ __device__ __forceinline__ void panel_norm_share(const PanelParams& p, int rhs, 
         const double* src = p.norms + ((long long)q * p.k + rhs) * 4;
         a += src[0];
         b += src[1];
-        e = (src[2] > e || src[2] != src[2]) ? src[2] : e;
+        e = nan_max(e, src[2]);
     }
+}
+
+// The steps of the reduce and the line search that k_panel_reduce and k_panel_reduce_upd share.
+// S of a thread's 4 consecutive rows of one RHS: the sum of the chunk slabs at `src` (fp64, chunk order).
+// Chunks go in groups of 8 with every load of a group issued before its adds (one memory round trip per
+// group instead of one per chunk; no per-element condition inside a group, which would make hipcc wait
+// for each load), the adds in chunk order.  Scalars in and the sums out by value: with the params struct
+// and the caller's array passed by reference hipcc kept more of k_panel_reduce_upd's loads in flight
+// (k_panel_reduce_upd<4>: 150 -> 218 VGPRs, 3 -> 2 waves per SIMD, which the co-residency check counts).
+__device__ __forceinline__ double4 panel_slab_sum4(const float* src, long long cstride, int kchunks) {
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    auto add = [&](const float4& v) {
+        s0 += (double)v.x;
+        s1 += (double)v.y;
+        s2 += (double)v.z;
+        s3 += (double)v.w;
+    };
+    int c = 0;
+    for (; c + 8 <= kchunks; c += 8) {
+        float4 v[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) v[q] = *reinterpret_cast<const float4*>(src + (c + q) * cstride);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) add(v[q]);
+    }
+    for (; c < kchunks; ++c) add(*reinterpret_cast<const float4*>(src + c * cstride));
+    return make_double4(s0, s1, s2, s3);
+}
+// the line-search partials r.s and s.s of those 4 rows
+__device__ __forceinline__ void panel_ls_partial4(const double (&r)[4], const double (&s)[4], double& rs,
+                                                  double& ss) {
+    rs = 0.0, ss = 0.0;
+    rs = fma(r[0], s[0], rs); rs = fma(r[1], s[1], rs);
+    rs = fma(r[2], s[2], rs); rs = fma(r[3], s[3], rs);
+    ss = fma(s[0], s[0], ss); ss = fma(s[1], s[1], ss);
+    ss = fma(s[2], s[2], ss); ss = fma(s[3], s[3], ss);
+}
+// ... summed over each wave into the group's LDS rows (then a barrier, then panel_publish_partials)
+__device__ __forceinline__ void panel_ls_waves(double rs, double ss, double (&sr)[kWaves], double (&sq)[kWaves]) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    rs = wave_sum(rs);
+    ss = wave_sum(ss);
+    if (lane == 0) { sr[wave] = rs; sq[wave] = ss; }
+}
+// thread 0: the block's U groups' partials (the 4 waves added in order) to p.lsp, groups grp0 .., then the
+// block's arrival at its RHS's counter; returns the count before it.
+// No agent fences: the partials are stored sc1 by this lane, which waits vmcnt(0) before its add, and
+// the last block reads them sc1 after its add returned (row 1 of MI355X_MICROARCH.md's table of sc1
+// hand-offs; the fence pair measured +36 us per launch, see op_arrive_last)
+template <int U>
+__device__ __forceinline__ unsigned long long panel_publish_partials(const PanelParams& p, int rhs, int grp0,
+                                                                     const double (&sr)[U][kWaves],
+                                                                     const double (&sq)[U][kWaves]) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        double* dst = p.lsp + ((long long)(grp0 + u) * p.k + rhs) * 2;
+        panel_st_sc1(dst, ((sr[u][0] + sr[u][1]) + sr[u][2]) + sr[u][3]);
+        panel_st_sc1(dst + 1, ((sq[u][0] + sq[u][1]) + sq[u][2]) + sq[u][3]);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    return __hip_atomic_fetch_add(p.cnt + rhs, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // S = sum over chunks (fp64, fixed order); line-search partials per RHS and
@@ -964,65 +992,32 @@ __global__ __launch_bounds__(kThreads) void k_panel_reduce(PanelParams p, double
     double na = 0.0, nb = 0.0, ne = 0.0;
     if (mode) panel_norm_share(p, rhs, na, nb, ne);
     if (i < p.m) {
-        double s[4] = {0.0, 0.0, 0.0, 0.0};
         // the residual rows for the line-search partials, loaded up front (in flight with the chunk
         // loads; p.R is a valid buffer in mode 0 too, where they go unused)
         const double* rp = p.R + (long long)rhs * p.m + i;
         const double2 r01 = *reinterpret_cast<const double2*>(rp);
         const double2 r23 = *reinterpret_cast<const double2*>(rp + 2);
-        const float* src = p.Sslab + (long long)rhs * p.m + i;
-        const long long cstride = (long long)p.k * p.m;
         unsigned wv = 0;
         if constexpr (MK) wv = *reinterpret_cast<const unsigned*>(p.W + (long long)rhs * p.m + i);
-        auto add = [&](const float4& v) {
-            s[0] += (double)v.x;
-            s[1] += (double)v.y;
-            s[2] += (double)v.z;
-            s[3] += (double)v.w;
-        };
-        // chunks in groups of 8 with every load of a group issued before its adds (one memory round
-        // trip per group instead of one per chunk; no per-element condition inside a group, which
-        // would make hipcc wait for each load), the adds in chunk order as before
-        int c = 0;
-        for (; c + 8 <= p.kchunks; c += 8) {
-            float4 v[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) v[q] = *reinterpret_cast<const float4*>(src + (c + q) * cstride);
-#pragma unroll
-            for (int q = 0; q < 8; ++q) add(v[q]);
-        }
-        for (; c < p.kchunks; ++c) add(*reinterpret_cast<const float4*>(src + c * cstride));
+        const double4 t = panel_slab_sum4(p.Sslab + (long long)rhs * p.m + i, (long long)p.k * p.m, p.kchunks);
+        double s[4] = {t.x, t.y, t.z, t.w};
         if constexpr (MK) panel_mask4(wv, s);
         const long long e = (long long)rhs * p.m + i;
         put(Sout, e, make_double2(s[0], s[1]));
         put(Sout, e + 2, make_double2(s[2], s[3]));
         if (mode) {
-            rs = fma(r01.x, s[0], rs); rs = fma(r01.y, s[1], rs);
-            rs = fma(r23.x, s[2], rs); rs = fma(r23.y, s[3], rs);
-            ss = fma(s[0], s[0], ss); ss = fma(s[1], s[1], ss);
-            ss = fma(s[2], s[2], ss); ss = fma(s[3], s[3], ss);
+            const double r[4] = {r01.x, r01.y, r23.x, r23.y};
+            panel_ls_partial4(r, s, rs, ss);
         }
     }
     if (!mode) return;
-    __shared__ double sr[kWaves], sq[kWaves];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    rs = wave_sum(rs);
-    ss = wave_sum(ss);
-    if (lane == 0) { sr[wave] = rs; sq[wave] = ss; }
+    __shared__ double sr[1][kWaves], sq[1][kWaves];
+    panel_ls_waves(rs, ss, sr[0], sq[0]);
     __syncthreads();
     __shared__ int last;
     if (threadIdx.x == 0) {
-        double* dst = p.lsp + ((long long)grp * p.k + rhs) * 2;
-        panel_st_sc1(dst, ((sr[0] + sr[1]) + sr[2]) + sr[3]);
-        panel_st_sc1(dst + 1, ((sq[0] + sq[1]) + sq[2]) + sq[3]);
         const unsigned long long ng = (unsigned long long)((p.m + kLspRows - 1) / kLspRows);
-        // no agent fences: the partials are stored sc1 by this lane, which waits vmcnt(0) before its
-        // add, and the last block reads them sc1 after its add returned (row 1 of MI355X_MICROARCH.md's
-        // table of sc1 hand-offs; the fence pair measured +36 us per launch, see op_arrive_last)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned long long old = __hip_atomic_fetch_add(p.cnt + rhs, 1ull, __ATOMIC_RELAXED,
-                                                              __HIP_MEMORY_SCOPE_AGENT);
-        last = ((old + 1) % ng) == 0;
+        last = ((panel_publish_partials<1>(p, rhs, grp, sr, sq) + 1) % ng) == 0;
     }
     __syncthreads();
     if (last) panel_step_rhs<true>(p, rhs, na, nb, ne);
@@ -1062,7 +1057,7 @@ __device__ void panel_step_rhs(const PanelParams& p, int rhs, double a, double b
         a = ((s3[0][0] + s3[0][1]) + s3[0][2]) + s3[0][3];
         b = ((s3[1][0] + s3[1][1]) + s3[1][2]) + s3[1][3];
         e = s3[2][0];
-        for (int q = 1; q < kWaves; ++q) e = (s3[2][q] > e || s3[2][q] != s3[2][q]) ? s3[2][q] : e;
+        for (int q = 1; q < kWaves; ++q) e = nan_max(e, s3[2][q]);
         const double r1 = rs + p.mu[rhs] * (a - b);
         // write-through: k_panel_reduce_upd's other blocks read them in the same launch
         panel_st_sc1(p.gamma + rhs, (ss == 0.0) ? 0.0 : proj(-r1 / ss, 0.0, 1.0));
@@ -1071,14 +1066,16 @@ __device__ void panel_step_rhs(const PanelParams& p, int rhs, double a, double b
     }
 }
 
-// end of an iteration (wave 0 of block 0 of the update launch): the max error over the RHS
-// (one load per lane, then the wave max -- a serial loop over k dependent loads cost ~10 us),
-// the error record, t + 1; `pending`: x += gamma D' is left to the next pass-1 epilogue
+// end of an iteration (one wave: wave 0 of block 0 of the update launch, or of k_panel_reduce_upd's block
+// that finished the last line search): the max error over the RHS (one load per lane, then the wave max
+// -- a serial loop over k dependent loads cost ~10 us), the error record, t + 1; `pending`: x += gamma D'
+// is left to the next pass-1 epilogue.  SC1: err_rhs was published (sc1) by other blocks of this launch
+template <bool SC1>
 __device__ __forceinline__ void panel_bump_t(const PanelParams& p, bool pending) {
     double e = 0.0;
     for (int j = threadIdx.x; j < p.k; j += 64) {
-        const double v = p.err_rhs[j];
-        e = (v > e || v != v) ? v : e;
+        const double v = SC1 ? panel_ld_sc1(p.err_rhs + j) : p.err_rhs[j];
+        e = nan_max(e, v);
     }
     e = wave_max(e);
     if (threadIdx.x == 0) {
@@ -1091,16 +1088,24 @@ __device__ __forceinline__ void panel_bump_t(const PanelParams& p, bool pending)
     }
 }
 
-// carried gradient (one feature block): the next pass 1's operand V = gamma S + E (cflag & 3 == 1; 2: the
-// iteration's G was exact, E restarts at 0), its bf16 image to Sh and the rounding error back to E;
-// cflag & 4: R's hi / lo images are not written (no exact pass 1 reads them before the next update)
-__device__ __forceinline__ void panel_put_carry(const PanelParams& p, int cflag, long long e, long long re,
-                                                double g, const double2& s01, const double2& s23) {
+// The residual update of a thread's 4 consecutive rows of one RHS (fp64 index e, operand image index re):
+// panel_r_update4, shared by k_panel_update1 and k_panel_reduce_upd (k_panel_update keeps its own R
+// arithmetic, see there, and shares the carried operand).
+// cflag: the carried gradient's operand -- 0 none; cflag & 3 == 1: V = gamma S + E; 2: V = gamma S (the
+// iteration's G was exact, E restarts at 0); cflag & 4: R's hi / lo images are not written (no exact
+// pass 1 reads them before the next update).
+// The operand's E is the caller's to load (panel_carry_e), so k_panel_reduce_upd can do it ahead of its
+// line search.
+__device__ __forceinline__ float4 panel_carry_e(const PanelParams& p, int cflag, long long e) {
+    return (cflag & 3) == 1 ? *reinterpret_cast<const float4*>(p.Ec + e) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+// carried gradient (one feature block): the next pass 1's operand V = gamma S + E, its bf16 image to Sh
+// and the rounding error back to E
+__device__ __forceinline__ void panel_put_carry(const PanelParams& p, long long e, long long re, double g,
+                                                const double (&s)[4], const float4& e4) {
     typedef __bf16 bf16x4c __attribute__((ext_vector_type(4)));
-    float4 e4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if ((cflag & 3) == 1) e4 = *reinterpret_cast<const float4*>(p.Ec + e);
-    const double v[4] = {(double)e4.x + g * s01.x, (double)e4.y + g * s01.y, (double)e4.z + g * s23.x,
-                         (double)e4.w + g * s23.y};
+    const double v[4] = {(double)e4.x + g * s[0], (double)e4.y + g * s[1], (double)e4.z + g * s[2],
+                         (double)e4.w + g * s[3]};
     __bf16 h[4];
     float r[4];
 #pragma unroll
@@ -1110,6 +1115,24 @@ __device__ __forceinline__ void panel_put_carry(const PanelParams& p, int cflag,
     }
     *reinterpret_cast<bf16x4c*>(p.Sh + re) = bf16x4c{h[0], h[1], h[2], h[3]};
     *reinterpret_cast<float4*>(p.Ec + e) = make_float4(r[0], r[1], r[2], r[3]);
+}
+// one feature block: R <- R + gamma S from the rows' old R (r) and S (s) (= Ax + gamma S - B; Ax is not
+// kept), the carried operand when cflag asks for it, R's hi / lo images unless cflag & 4
+__device__ __forceinline__ void panel_r_update4(const PanelParams& p, int cflag, long long e, long long re,
+                                                double g, const double (&r)[4], const double (&s)[4],
+                                                const float4& e4) {
+    typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
+    const double rn[4] = {r[0] + g * s[0], r[1] + g * s[1], r[2] + g * s[2], r[3] + g * s[3]};
+    if (cflag) panel_put_carry(p, e, re, g, s, e4);
+    put(p.R, e, make_double2(rn[0], rn[1]));
+    put(p.R, e + 2, make_double2(rn[2], rn[3]));
+    if (!(cflag & 4)) {
+        __bf16 hi[4], lo[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) split_bf16(rn[q], hi[q], lo[q]);
+        put(p.Rh, re, bf16x4v{hi[0], hi[1], hi[2], hi[3]});
+        put(p.Rl, re, bf16x4v{lo[0], lo[1], lo[2], lo[3]});
+    }
 }
 
 // x_j += gamma_j D'_j ; Ax_j += gamma_j S_j ; R = sum_b Ax_b - B ; split R.
@@ -1127,29 +1150,10 @@ __global__ __launch_bounds__(kThreads) void k_panel_update(PanelParams p, int cf
     const unsigned ux = (unsigned)(nx / 8), ur = (unsigned)(nr / 4);
     const unsigned nu = ux + ur;
     const unsigned w8 = (unsigned)(p.w / 8), m4 = (unsigned)(p.m / 4);
-    typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
     typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
     for (unsigned u = blockIdx.x * kThreads + threadIdx.x; u < nu; u += gridDim.x * kThreads) {
         if (u < ux) {
-            const long long e = 8ll * u;
-            const unsigned rhs = u / w8;
-            const long long de = (long long)rhs * p.ldd + (e - (long long)rhs * p.w);   // operand image index
-            const double g = p.gamma[rhs];
-            const bf16x8v dh = *reinterpret_cast<const bf16x8v*>(p.Dh + de);
-            bf16x8v dl;
-            if constexpr (DS == 2) dl = *reinterpret_cast<const bf16x8v*>(p.Dl + de);
-            float* xp = p.X + (long long)mb * nx + e;
-            float4 x0 = *reinterpret_cast<const float4*>(xp);
-            float4 x1 = *reinterpret_cast<const float4*>(xp + 4);
-            float xs[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                double dq = (double)(float)dh[q];
-                if constexpr (DS == 2) dq += (double)(float)dl[q];
-                xs[q] = (float)((double)xs[q] + g * dq);
-            }
-            *reinterpret_cast<float4*>(xp) = make_float4(xs[0], xs[1], xs[2], xs[3]);
-            *reinterpret_cast<float4*>(xp + 4) = make_float4(xs[4], xs[5], xs[6], xs[7]);
+            panel_x_update8<DS>(p, p.X + (long long)mb * nx, u, w8);
         }
         else {
             const unsigned v = u - ux;
@@ -1160,6 +1164,9 @@ __global__ __launch_bounds__(kThreads) void k_panel_update(PanelParams p, int cf
             double r[4];
             __bf16 hi[4], lo[4];
             if constexpr (NB1) {
+                // Not panel_r_update4: in this kernel hipcc contracts r + g * s to an fma, in k_panel_update1
+                // and k_panel_reduce_upd (where g * s is shared with the carried operand) it does not, so
+                // the helper here would change R's last bit against what this form has always computed
                 const double2 r01 = *reinterpret_cast<const double2*>(p.R + e);
                 const double2 r23 = *reinterpret_cast<const double2*>(p.R + e + 2);
                 const double2 s01 = *reinterpret_cast<const double2*>(p.S + e);
@@ -1168,7 +1175,8 @@ __global__ __launch_bounds__(kThreads) void k_panel_update(PanelParams p, int cf
                 r[2] = r23.x + g * s23.x; r[3] = r23.y + g * s23.y;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) split_bf16(r[q], hi[q], lo[q]);
-                if (cflag) panel_put_carry(p, cflag, e, re, g, s01, s23);
+                const double s[4] = {s01.x, s01.y, s23.x, s23.y};
+                if (cflag) panel_put_carry(p, e, re, g, s, panel_carry_e(p, cflag, e));
             } else {
                 double* ap = p.Ax + (long long)mb * nr + e;
                 double a[4], acc[4];
@@ -1195,7 +1203,7 @@ __global__ __launch_bounds__(kThreads) void k_panel_update(PanelParams p, int cf
             }
         }
     }
-    if (blockIdx.x == 0 && threadIdx.x < 64) panel_bump_t(p, false);
+    if (blockIdx.x == 0 && threadIdx.x < 64) panel_bump_t<false>(p, false);
 }
 
 // One feature block: R_j += gamma_j S_j (= Ax_j + gamma_j S_j - B_j; Ax is not kept) and its
@@ -1204,7 +1212,6 @@ __global__ __launch_bounds__(kThreads) void k_panel_update(PanelParams p, int cf
 __global__ __launch_bounds__(kThreads) void k_panel_update1(PanelParams p, int cflag) {
     const long long nr = (long long)p.k * p.m;
     const unsigned ur = (unsigned)(nr / 4), m4 = (unsigned)(p.m / 4);
-    typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
     for (unsigned v = blockIdx.x * kThreads + threadIdx.x; v < ur; v += gridDim.x * kThreads) {
         const long long e = 4ll * v;
         const unsigned rhs = v / m4;
@@ -1214,19 +1221,10 @@ __global__ __launch_bounds__(kThreads) void k_panel_update1(PanelParams p, int c
         const double2 r23 = *reinterpret_cast<const double2*>(p.R + e + 2);
         const double2 s01 = *reinterpret_cast<const double2*>(p.S + e);
         const double2 s23 = *reinterpret_cast<const double2*>(p.S + e + 2);
-        const double r[4] = {r01.x + g * s01.x, r01.y + g * s01.y, r23.x + g * s23.x, r23.y + g * s23.y};
-        if (cflag) panel_put_carry(p, cflag, e, re, g, s01, s23);
-        __bf16 hi[4], lo[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) split_bf16(r[q], hi[q], lo[q]);
-        put(p.R, e, make_double2(r[0], r[1]));
-        put(p.R, e + 2, make_double2(r[2], r[3]));
-        if (!(cflag & 4)) {
-            put(p.Rh, re, bf16x4v{hi[0], hi[1], hi[2], hi[3]});
-            put(p.Rl, re, bf16x4v{lo[0], lo[1], lo[2], lo[3]});
-        }
+        const double r[4] = {r01.x, r01.y, r23.x, r23.y}, s[4] = {s01.x, s01.y, s23.x, s23.y};
+        panel_r_update4(p, cflag, e, re, g, r, s, panel_carry_e(p, cflag, e));
     }
-    if (blockIdx.x == 0 && threadIdx.x < 64) panel_bump_t(p, true);
+    if (blockIdx.x == 0 && threadIdx.x < 64) panel_bump_t<false>(p, true);
 }
 
 // One feature block with x deferred (the default configs[4] iteration): k_panel_reduce (S = the
@@ -1251,7 +1249,6 @@ template <int U, bool MK = false>
 __global__ __launch_bounds__(kThreads) void k_panel_reduce_upd(PanelParams p, int cflag, int G) {
     const int rhs = blockIdx.x % p.k;
     const int g = blockIdx.x / p.k;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double na = 0.0, nb = 0.0, ne = 0.0;
     panel_norm_share(p, rhs, na, nb, ne);
     const long long cstride = (long long)p.k * p.m;
@@ -1263,56 +1260,27 @@ __global__ __launch_bounds__(kThreads) void k_panel_reduce_upd(PanelParams p, in
         const double2 r01 = *reinterpret_cast<const double2*>(p.R + e);
         const double2 r23 = *reinterpret_cast<const double2*>(p.R + e + 2);
         r[u][0] = r01.x; r[u][1] = r01.y; r[u][2] = r23.x; r[u][3] = r23.y;
-        ev[u] = (cflag & 3) == 1 ? *reinterpret_cast<const float4*>(p.Ec + e) : make_float4(0.f, 0.f, 0.f, 0.f);
+        ev[u] = panel_carry_e(p, cflag, e);
         unsigned wv = 0;
         if constexpr (MK) wv = *reinterpret_cast<const unsigned*>(p.W + e);
-        const float* src = p.Sslab + e;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) s[u][q] = 0.0;
-        int c = 0;
-        for (; c + 8 <= p.kchunks; c += 8) {   // 8 loads in flight, the adds in chunk order
-            float4 v[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) v[q] = *reinterpret_cast<const float4*>(src + (c + q) * cstride);
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                s[u][0] += (double)v[q].x; s[u][1] += (double)v[q].y; s[u][2] += (double)v[q].z; s[u][3] += (double)v[q].w;
-            }
-        }
-        for (; c < p.kchunks; ++c) {
-            const float4 v = *reinterpret_cast<const float4*>(src + c * cstride);
-            s[u][0] += (double)v.x; s[u][1] += (double)v.y; s[u][2] += (double)v.z; s[u][3] += (double)v.w;
-        }
+        const double4 t = panel_slab_sum4(p.Sslab + e, cstride, p.kchunks);
+        s[u][0] = t.x; s[u][1] = t.y; s[u][2] = t.z; s[u][3] = t.w;
         if constexpr (MK) panel_mask4(wv, s[u]);
     }
     // per-group line-search partials, in k_panel_reduce's order
     __shared__ double sr[U][kWaves], sq[U][kWaves];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-        double rs = 0.0, ss = 0.0;
-        rs = fma(r[u][0], s[u][0], rs); rs = fma(r[u][1], s[u][1], rs);
-        rs = fma(r[u][2], s[u][2], rs); rs = fma(r[u][3], s[u][3], rs);
-        ss = fma(s[u][0], s[u][0], ss); ss = fma(s[u][1], s[u][1], ss);
-        ss = fma(s[u][2], s[u][2], ss); ss = fma(s[u][3], s[u][3], ss);
-        rs = wave_sum(rs);
-        ss = wave_sum(ss);
-        if (lane == 0) { sr[u][wave] = rs; sq[u][wave] = ss; }
+        double rs, ss;
+        panel_ls_partial4(r[u], s[u], rs, ss);
+        panel_ls_waves(rs, ss, sr[u], sq[u]);
     }
     __syncthreads();
     __shared__ int last, ok;
     __shared__ unsigned long long target;
     __shared__ double gsh;
     if (threadIdx.x == 0) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            double* dst = p.lsp + ((long long)(g * U + u) * p.k + rhs) * 2;
-            panel_st_sc1(dst, ((sr[u][0] + sr[u][1]) + sr[u][2]) + sr[u][3]);
-            panel_st_sc1(dst + 1, ((sq[u][0] + sq[u][1]) + sq[u][2]) + sq[u][3]);
-        }
-        // the sc1 hand-off of k_panel_reduce (no agent fences; see op_arrive_last)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned long long old = __hip_atomic_fetch_add(p.cnt + rhs, 1ull, __ATOMIC_RELAXED,
-                                                              __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned long long old = panel_publish_partials<U>(p, rhs, g * U, sr, sq);
         last = ((old + 1) % (unsigned long long)G) == 0;
         target = (old / (unsigned long long)G + 1) * (unsigned long long)G;
         ok = 1;
@@ -1341,53 +1309,14 @@ __global__ __launch_bounds__(kThreads) void k_panel_reduce_upd(PanelParams p, in
     __syncthreads();
     if (!ok) return;   // block-uniform: nothing is updated (bpgl_panel_status reports the failure)
     const double gm = gsh;
-    typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const long long e = (long long)rhs * p.m + (long long)(g * U + u) * kLspRows + 4 * threadIdx.x;
         const long long re = (long long)rhs * p.ldr + (e - (long long)rhs * p.m);
-        double rn[4];
-        __bf16 hi[4], lo[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) rn[q] = r[u][q] + gm * s[u][q];
-        if (cflag) {   // the carried operand V = E + gamma S (panel_put_carry, E preloaded)
-            const float e4[4] = {ev[u].x, ev[u].y, ev[u].z, ev[u].w};
-            __bf16 h[4];
-            float rr[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const double v = (double)e4[q] + gm * s[u][q];
-                h[q] = to_bf16((float)v);
-                rr[q] = (float)(v - (double)(float)h[q]);
-            }
-            *reinterpret_cast<bf16x4v*>(p.Sh + re) = bf16x4v{h[0], h[1], h[2], h[3]};
-            *reinterpret_cast<float4*>(p.Ec + e) = make_float4(rr[0], rr[1], rr[2], rr[3]);
-        }
-        put(p.R, e, make_double2(rn[0], rn[1]));
-        put(p.R, e + 2, make_double2(rn[2], rn[3]));
-        if (!(cflag & 4)) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) split_bf16(rn[q], hi[q], lo[q]);
-            put(p.Rh, re, bf16x4v{hi[0], hi[1], hi[2], hi[3]});
-            put(p.Rl, re, bf16x4v{lo[0], lo[1], lo[2], lo[3]});
-        }
+        panel_r_update4(p, cflag, e, re, gm, r[u], s[u], ev[u]);
     }
-    if (last == 2 && threadIdx.x < 64) {   // every RHS's err_rhs is published (sc1): end the iteration
-        double e = 0.0;
-        for (int j = threadIdx.x; j < p.k; j += 64) {
-            const double v = panel_ld_sc1(p.err_rhs + j);
-            e = (v > e || v != v) ? v : e;
-        }
-        e = wave_max(e);
-        if (threadIdx.x == 0) {
-            const long long t = p.st->t;
-            if (p.err_iter && t < p.rec_len) p.err_iter[t] = e;
-            p.st->last_err = e;
-            p.st->t = t + 1;
-            p.st->iters = t + 1;
-            p.st->pending = 1;
-        }
-    }
+    // every RHS's err_rhs is published (sc1): end the iteration
+    if (last == 2 && threadIdx.x < 64) panel_bump_t<true>(p, true);
 }
 
 // apply a pending x += gamma D' (one feature block) -- the end of every bpgl_panel_step, so the
@@ -1396,29 +1325,9 @@ template <int DS>
 __global__ __launch_bounds__(kThreads) void k_panel_flush(PanelParams p) {
     if (p.st->pending == 0) return;
     const long long nx = (long long)p.k * p.w;
-    typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
     const unsigned w8 = (unsigned)(p.w / 8);
-    for (unsigned u = blockIdx.x * kThreads + threadIdx.x; u < (unsigned)(nx / 8); u += gridDim.x * kThreads) {
-        const long long e = 8ll * u;
-        const unsigned rhs = u / w8;
-        const long long de = (long long)rhs * p.ldd + (e - (long long)rhs * p.w);   // operand image index
-        const double g = p.gamma[rhs];
-        const bf16x8v dh = *reinterpret_cast<const bf16x8v*>(p.Dh + de);
-        bf16x8v dl;
-        if constexpr (DS == 2) dl = *reinterpret_cast<const bf16x8v*>(p.Dl + de);
-        float* xp = p.X + e;
-        float4 x0 = *reinterpret_cast<const float4*>(xp);
-        float4 x1 = *reinterpret_cast<const float4*>(xp + 4);
-        float xs[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            double dq = (double)(float)dh[q];
-            if constexpr (DS == 2) dq += (double)(float)dl[q];
-            xs[q] = (float)((double)xs[q] + g * dq);
-        }
-        *reinterpret_cast<float4*>(xp) = make_float4(xs[0], xs[1], xs[2], xs[3]);
-        *reinterpret_cast<float4*>(xp + 4) = make_float4(xs[4], xs[5], xs[6], xs[7]);
-    }
+    for (unsigned u = blockIdx.x * kThreads + threadIdx.x; u < (unsigned)(nx / 8); u += gridDim.x * kThreads)
+        panel_x_update8<DS>(p, p.X, u, w8);
 }
 __global__ void k_panel_clear_pending(PanelParams p) {
     if (threadIdx.x == 0) p.st->pending = 0;

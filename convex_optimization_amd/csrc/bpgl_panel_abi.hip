@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/bpgl.h"
@@ -20,6 +21,12 @@ using namespace bpgl_host;
 // panel path (k right-hand sides, bf16 A, MFMA): BASELINE configs[4]
 // ===========================================================================
 constexpr int kPanelKinds = 5;   // pass1, pass2, reduce, step, update
+
+// byte offsets of the scratch regions (panel_layout), in the order they are laid out
+struct PanelLayout {
+    int64_t st, Rh, Rl, Dh, Dl, X, Ax, B, R, diag, rec, Sslab, S, norms, lsp, mu, gamma, err_rhs, cnt, ready, lsdone, Gc,
+        Sh, Ec, At, A1t, gpart, gparts, gcounts, gres, W, Bh, ghold, total;
+};
 
 struct bpgl_panel {
     int device = 0;
@@ -50,16 +57,31 @@ struct bpgl_panel {
     hipEvent_t gap_ev[3] = {};    // bpgl_panel_gap: before product 1, between the products, after product 2
     int64_t gap_ns[2] = {};       // the last call's two products (each with its fold), stats "gap_prod1_ns" / "gap_prod2_ns"
     bool masked = false;          // bpgl_panel_set_row_mask installed a mask: the MK kernel variants run
+    char* scratch = nullptr;      // the caller's scratch and its layout (bpgl_panel_bind)
+    PanelLayout L{};
+    template <typename T>
+    T* at(int64_t off) const { return reinterpret_cast<T*>(scratch + off); }   // the region at L.<name>
     int64_t ldr() const { return m; }
     int64_t ldd() const { return w; }
 };
 
 namespace {
 
-struct PanelLayout {
-    int64_t st, Rh, Rl, Dh, Dl, X, Ax, B, R, diag, rec, Sslab, S, norms, lsp, mu, gamma, err_rhs, cnt, ready, lsdone, Gc,
-        Sh, Ec, At, A1t, gpart, gparts, gcounts, gres, W, Bh, ghold, total;
-};
+// f(std::integral_constant<int, V>{}) for the V among V0, Vs... that equals v (the last one when none
+// does): a run-time value picks a template argument, as static_for does on the device
+template <int V0, int... Vs, typename F>
+auto dispatch(int v, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) {
+        return f(std::integral_constant<int, V0>{});
+    } else {
+        if (v == V0) return f(std::integral_constant<int, V0>{});
+        return dispatch<Vs...>(v, f);
+    }
+}
+// NT, the 16-wide RHS tiles of the k right-hand sides (16, 32, 64 or 128: bpgl_panel_create)
+template <typename F>
+auto dispatch_nt(int k, F&& f) { return dispatch<1, 2, 4, 8>(k / 16, f); }
+
 // bpgl_panel_gap: the chunks of a product's reduction (`stages` 32-deep stages, `tiles` 64-output
 // tiles) -- doubled while the product has fewer than kPgBlocksTarget blocks and a chunk keeps two
 // stages.  A function of the shape alone.
@@ -74,12 +96,8 @@ int pgap_nparts(const bpgl_panel* c) {
 template <int PROD>
 int pgap_prod(bpgl_panel* c, const PanelGapArgs& a, dim3 grid) {
     const dim3 blk(kThreads);
-    switch (c->k) {
-        case 16: hipLaunchKernelGGL((k_pgap_prod<1, PROD>), grid, blk, 0, c->stream, a); break;
-        case 32: hipLaunchKernelGGL((k_pgap_prod<2, PROD>), grid, blk, 0, c->stream, a); break;
-        case 64: hipLaunchKernelGGL((k_pgap_prod<4, PROD>), grid, blk, 0, c->stream, a); break;
-        default: hipLaunchKernelGGL((k_pgap_prod<8, PROD>), grid, blk, 0, c->stream, a); break;
-    }
+    const auto prod = dispatch_nt(c->k, [](auto nt) { return &k_pgap_prod<decltype(nt)::value, PROD>; });
+    hipLaunchKernelGGL(prod, grid, blk, 0, c->stream, a);
     LAUNCH_CHECK("k_pgap_prod");
     const dim3 fgrid((unsigned)cdiv((int64_t)c->k * (PROD == 1 ? c->m : c->n), kThreads));
     if (PROD == 1 && c->masked) hipLaunchKernelGGL((k_pgap_fold<1, true>), fgrid, blk, 0, c->stream, a);
@@ -117,8 +135,8 @@ PanelLayout panel_layout(const bpgl_panel* c) {
     L.Gc = k.take(carry ? 4 * kw : 0);                           // the carried gradient (fp32)
     L.Sh = k.take(carry ? 2 * (int64_t)c->k * c->ldr() : 0);     // the carried product's bf16 operand
     L.Ec = k.take(carry ? 4 * km : 0);                           // its rounding error, fed into the next one (fp32)
-    L.At = k.take(kPanelTiled2 ? 2 * c->m * c->n : 0);            // pass 2's tiled copy of A (bf16)
-    L.A1t = k.take(kPanelTiled1 ? 2 * c->m * c->n : 0);           // pass 1's tiled copy of A (bf16)
+    L.At = k.take(2 * c->m * c->n);                              // pass 2's tiled copy of A (bf16)
+    L.A1t = k.take(2 * c->m * c->n);                             // pass 1's tiled copy of A (bf16)
     // bpgl_panel_gap (bpgl_panel_gap.h): the two products' chunk partials (one buffer, the larger), the
     // per-RHS partials, the screen's per-block counts and the results.  Laid out last: nothing before
     // them moves.
@@ -146,58 +164,31 @@ int panel_ilv(const bpgl_panel* c, int which, int ns) {
     if (v >= 0) return v;
     return which == 0 ? 2 : (ns == 1 && c->k >= 64 ? 2 : 1);
 }
-template <int NT, int ILV, int NS>
-int panel_launch_nt(bpgl_panel* c, int which, int fixed_block, double* out, int mode) {
-    switch (which) {
-        case 0:
-            {   // carried-gradient forms (one feature block)
-                if (mode && c->gm_cur == 1) {
-                    hipLaunchKernelGGL((k_panel_pass1<NT, 1, ILV, NS, 1>), dim3((unsigned)(c->w / kPanelRows)),
-                                       dim3(PanelGeo<NT, 2>::T), 0, c->stream, c->p, fixed_block, out);
-                    LAUNCH_CHECK("k_panel_pass1");
-                    break;
-                }
-                if (mode && c->gm_cur == 2) {
-                    hipLaunchKernelGGL((k_panel_pass1<NT, 1, ILV, NS, 2>), dim3((unsigned)(c->w / kPanelRows)),
-                                       dim3(PanelGeo<NT, 2>::T), 0, c->stream, c->p, fixed_block, out);
-                    LAUNCH_CHECK("k_panel_pass1");
-                    break;
-                }
-            }
-            if (mode) hipLaunchKernelGGL((k_panel_pass1<NT, 1, ILV, NS>), dim3((unsigned)(c->w / kPanelRows)),
-                                         dim3(PanelGeo<NT, 2>::T), 0, c->stream, c->p, fixed_block, out);
-            else hipLaunchKernelGGL((k_panel_pass1<NT, 0, ILV, 2>), dim3((unsigned)(c->w / kPanelRows)),
-                                    dim3(PanelGeo<NT, 2>::T), 0, c->stream, c->p, fixed_block, out);
-            LAUNCH_CHECK("k_panel_pass1");
-            break;
-        case 1:
-            hipLaunchKernelGGL((k_panel_pass2<NT, ILV, NS>), dim3((unsigned)((c->m / kPanelRows) * c->kchunks)),
-                               dim3(PanelGeo<NT, NS>::T), 0, c->stream, c->p, fixed_block);
-            LAUNCH_CHECK("k_panel_pass2");
-            break;
-    }
-    return 0;
-}
-template <int NT, int NS>
-int panel_launch_ilv(bpgl_panel* c, int which, int fixed_block, double* out, int mode) {
-    switch (panel_ilv(c, which, NS)) {
-        case 0: return panel_launch_nt<NT, 0, NS>(c, which, fixed_block, out, mode);
-        case 1: return panel_launch_nt<NT, 1, NS>(c, which, fixed_block, out, mode);
-        default: return panel_launch_nt<NT, 2, NS>(c, which, fixed_block, out, mode);
-    }
-}
-template <int NS>
-int panel_launch_ns(bpgl_panel* c, int which, int fixed_block, double* out, int mode) {
-    switch (c->k) {
-        case 16: return panel_launch_ilv<1, NS>(c, which, fixed_block, out, mode);
-        case 32: return panel_launch_ilv<2, NS>(c, which, fixed_block, out, mode);
-        case 64: return panel_launch_ilv<4, NS>(c, which, fixed_block, out, mode);
-        default: return panel_launch_ilv<8, NS>(c, which, fixed_block, out, mode);
-    }
-}
+// pass 1 (which 0; mode 0: G to `out`, the API product; mode 1: the fused shrink in the form gm_cur names:
+// 0 plain, 1 exact + store G, 2 carried) or pass 2 (which 1) of block `fixed_block` (-1: the solver's)
 int panel_launch(bpgl_panel* c, int which, int fixed_block, double* out, int mode, int ns) {
-    return ns == 1 ? panel_launch_ns<1>(c, which, fixed_block, out, mode)
-                   : panel_launch_ns<2>(c, which, fixed_block, out, mode);
+    return dispatch_nt(c->k, [&](auto ntc) {
+        return dispatch<0, 1, 2>(panel_ilv(c, which, ns), [&](auto ilvc) {
+            return dispatch<1, 2>(ns, [&](auto nsc) {
+                constexpr int NT = decltype(ntc)::value, ILV = decltype(ilvc)::value, NS = decltype(nsc)::value;
+                if (which == 0) {
+                    void (*pass1)(PanelParams, int, double*) = &k_panel_pass1<NT, 0, ILV, 2>;
+                    if (mode)
+                        pass1 = dispatch<1, 2, 0>(c->gm_cur, [](auto gm) {
+                            return &k_panel_pass1<NT, 1, ILV, NS, decltype(gm)::value>;
+                        });
+                    hipLaunchKernelGGL(pass1, dim3((unsigned)(c->w / kPanelRows)), dim3(PanelGeo<NT, 2>::T), 0,
+                                       c->stream, c->p, fixed_block, out);
+                    LAUNCH_CHECK("k_panel_pass1");
+                } else {
+                    hipLaunchKernelGGL((k_panel_pass2<NT, ILV, NS>), dim3((unsigned)((c->m / kPanelRows) * c->kchunks)),
+                                       dim3(PanelGeo<NT, NS>::T), 0, c->stream, c->p, fixed_block);
+                    LAUNCH_CHECK("k_panel_pass2");
+                }
+                return 0;
+            });
+        });
+    });
 }
 bool panel_carry(const bpgl_panel* c) { return c->carry_g && c->nblock == 1; }
 int panel_pass(bpgl_panel* c, int which) { return panel_launch(c, which, -1, nullptr, 1, c->dsplit); }
@@ -214,24 +205,19 @@ bool panel_fused_geo(const bpgl_panel* c, int* G, int* U) {
     *U = (int)u;
     return true;
 }
-const void* panel_fused_fn(int U, bool masked) {
-    if (masked)
-        return U == 1 ? (const void*)k_panel_reduce_upd<1, true> : U == 2 ? (const void*)k_panel_reduce_upd<2, true>
-                                                                        : (const void*)k_panel_reduce_upd<4, true>;
-    return U == 1 ? (const void*)k_panel_reduce_upd<1> : U == 2 ? (const void*)k_panel_reduce_upd<2>
-                                                              : (const void*)k_panel_reduce_upd<4>;
+// the k_panel_reduce_upd variant of a geometry: what panel_fuse_check asks the occupancy of is what
+// panel_reduce_upd launches
+using PanelFusedFn = void (*)(PanelParams, int, int);
+PanelFusedFn panel_fused_fn(int U, bool masked) {
+    return dispatch<1, 2, 4>(U, [&](auto u) -> PanelFusedFn {
+        return masked ? &k_panel_reduce_upd<decltype(u)::value, true> : &k_panel_reduce_upd<decltype(u)::value, false>;
+    });
 }
 int panel_reduce_upd(bpgl_panel* c, int cflag) {
     int G = 0, U = 0;
     (void)panel_fused_geo(c, &G, &U);
-    const dim3 grid((unsigned)(c->k * G)), blk(kThreads);
-    if (c->masked) {
-        if (U == 1) hipLaunchKernelGGL((k_panel_reduce_upd<1, true>), grid, blk, 0, c->stream, c->p, cflag, G);
-        else if (U == 2) hipLaunchKernelGGL((k_panel_reduce_upd<2, true>), grid, blk, 0, c->stream, c->p, cflag, G);
-        else hipLaunchKernelGGL((k_panel_reduce_upd<4, true>), grid, blk, 0, c->stream, c->p, cflag, G);
-    } else if (U == 1) hipLaunchKernelGGL(k_panel_reduce_upd<1>, grid, blk, 0, c->stream, c->p, cflag, G);
-    else if (U == 2) hipLaunchKernelGGL(k_panel_reduce_upd<2>, grid, blk, 0, c->stream, c->p, cflag, G);
-    else hipLaunchKernelGGL(k_panel_reduce_upd<4>, grid, blk, 0, c->stream, c->p, cflag, G);
+    hipLaunchKernelGGL(panel_fused_fn(U, c->masked), dim3((unsigned)(c->k * G)), dim3(kThreads), 0, c->stream, c->p,
+                       cflag, G);
     LAUNCH_CHECK("k_panel_reduce_upd");
     return 0;
 }
@@ -243,7 +229,8 @@ void panel_fuse_check(bpgl_panel* c) {
     c->fuse_ok = 0;
     c->fuse_cus = 0;
     if (!panel_fused_geo(c, &G, &U)) return;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, panel_fused_fn(U, c->masked), kThreads, 0) != hipSuccess) {
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)panel_fused_fn(U, c->masked), kThreads, 0) !=
+        hipSuccess) {
         (void)hipGetLastError();   // the query's own error only
         return;
     }
@@ -302,13 +289,10 @@ int panel_iteration(bpgl_panel* c, int64_t it, bool exact = false, bool split_r 
         const int64_t n = (int64_t)c->k * c->w / 8 + (int64_t)c->k * c->m / 4;   // work units
         const dim3 ug((unsigned)std::min<int64_t>(cdiv(n, kThreads), 8192));
         const bool nb1 = c->nblock == 1;
-        if (c->dsplit == 1) {
-            if (nb1) hipLaunchKernelGGL((k_panel_update<1, true>), ug, dim3(kThreads), 0, c->stream, c->p, cflag);
-            else hipLaunchKernelGGL((k_panel_update<1, false>), ug, dim3(kThreads), 0, c->stream, c->p, cflag);
-        } else {
-            if (nb1) hipLaunchKernelGGL((k_panel_update<2, true>), ug, dim3(kThreads), 0, c->stream, c->p, cflag);
-            else hipLaunchKernelGGL((k_panel_update<2, false>), ug, dim3(kThreads), 0, c->stream, c->p, cflag);
-        }
+        const auto update = dispatch<1, 2>(c->dsplit, [&](auto ds) {
+            return nb1 ? &k_panel_update<decltype(ds)::value, true> : &k_panel_update<decltype(ds)::value, false>;
+        });
+        hipLaunchKernelGGL(update, ug, dim3(kThreads), 0, c->stream, c->p, cflag);
     }
     LAUNCH_CHECK("k_panel_update");
     panel_ev(c, it, 4, 1);
@@ -400,7 +384,8 @@ int bpgl_panel_bind(bpgl_panel* c, const void* A, int64_t lda, void* scratch, in
     const PanelLayout L = panel_layout(c);
     if (scratch_bytes < L.total) return fail(BPGL_E_SCRATCH, "scratch too small: %lld < %lld",
                                              (long long)scratch_bytes, (long long)L.total);
-    char* s = (char*)scratch;
+    c->scratch = (char*)scratch;
+    c->L = L;
     PanelParams& p = c->p;
     p = PanelParams{};
     p.A = (const __bf16*)A;
@@ -412,43 +397,46 @@ int bpgl_panel_bind(bpgl_panel* c, const void* A, int64_t lda, void* scratch, in
     p.kchunks = c->kchunks;
     p.ldr = c->ldr();
     p.ldd = c->ldd();
-    p.st = (PanelState*)(s + L.st);
-    p.Rh = (__bf16*)(s + L.Rh);
-    p.Rl = (__bf16*)(s + L.Rl);
-    p.Dh = (__bf16*)(s + L.Dh);
-    p.Dl = (__bf16*)(s + L.Dl);
-    p.X = (float*)(s + L.X);
-    p.Ax = (double*)(s + L.Ax);
-    p.B = (const double*)(s + L.B);
-    p.R = (double*)(s + L.R);
-    p.diag = (const double*)(s + L.diag);
-    p.rec = (const double*)(s + L.rec);
-    p.Sslab = (float*)(s + L.Sslab);
-    p.S = (double*)(s + L.S);
-    p.norms = (double*)(s + L.norms);
-    p.lsp = (double*)(s + L.lsp);
-    p.mu = (const double*)(s + L.mu);
-    p.gamma = (double*)(s + L.gamma);
-    p.err_rhs = (double*)(s + L.err_rhs);
-    p.cnt = (unsigned long long*)(s + L.cnt);
-    p.Gc = (float*)(s + L.Gc);
-    p.Ec = (float*)(s + L.Ec);
-    p.ready = (unsigned long long*)(s + L.ready);
-    p.lsdone = (unsigned long long*)(s + L.lsdone);
-    p.At = kPanelTiled2 ? (const __bf16*)(s + L.At) : nullptr;
-    p.A1t = kPanelTiled1 ? (const __bf16*)(s + L.A1t) : nullptr;
+    p.st = c->at<PanelState>(L.st);
+    p.Rh = c->at<__bf16>(L.Rh);
+    p.Rl = c->at<__bf16>(L.Rl);
+    p.Dh = c->at<__bf16>(L.Dh);
+    p.Dl = c->at<__bf16>(L.Dl);
+    p.X = c->at<float>(L.X);
+    p.Ax = c->at<double>(L.Ax);
+    p.B = c->at<double>(L.B);
+    p.R = c->at<double>(L.R);
+    p.diag = c->at<double>(L.diag);
+    p.rec = c->at<double>(L.rec);
+    p.Sslab = c->at<float>(L.Sslab);
+    p.S = c->at<double>(L.S);
+    p.norms = c->at<double>(L.norms);
+    p.lsp = c->at<double>(L.lsp);
+    p.mu = c->at<double>(L.mu);
+    p.gamma = c->at<double>(L.gamma);
+    p.err_rhs = c->at<double>(L.err_rhs);
+    p.cnt = c->at<unsigned long long>(L.cnt);
+    p.Gc = c->at<float>(L.Gc);
+    p.Ec = c->at<float>(L.Ec);
+    p.ready = c->at<unsigned long long>(L.ready);
+    p.lsdone = c->at<unsigned long long>(L.lsdone);
+    p.At = c->at<__bf16>(L.At);
+    p.A1t = c->at<__bf16>(L.A1t);
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemsetAsync(s, 0, L.At, c->stream));   // everything but the tiled A copies (laid out last)
-    if (kPanelTiled2) {
-        hipLaunchKernelGGL((k_panel_tile<256, 64, true>), dim3((unsigned)((c->m / 256) * (c->n / 64))), dim3(256), 0,
-                           c->stream, p.A, p.lda, c->n, const_cast<__bf16*>(p.At));
-        LAUNCH_CHECK("k_panel_tile");
-    }
-    if (kPanelTiled1) {
-        hipLaunchKernelGGL((k_panel_tile<64, 256, false>), dim3((unsigned)((c->m / 64) * (c->n / 256))), dim3(256), 0,
-                           c->stream, p.A, p.lda, c->n, const_cast<__bf16*>(p.A1t));
-        LAUNCH_CHECK("k_panel_tile");
-    }
+    // Cleared here: every region up to the tiled copies -- the state, counters and partials, the operand
+    // images, X, Ax, B, R, diag / rec and the carried gradient's G, operand and E -- so that nothing reads
+    // a stale value before its first write (the solver's own reset clears again what it must).  Not
+    // cleared, because each is written in full before it is read: At / A1t (the tile kernels below), the
+    // certificate's buffers gpart, gparts, gcounts, gres and ghold (every bpgl_panel_gap writes them first),
+    // W (bpgl_panel_set_row_mask, and p.W is null until then) and Bh (k_panel_mask_b at a masked reset; the
+    // certificate reads it only under a mask).
+    HIP_TRY(hipMemsetAsync(c->scratch, 0, L.At, c->stream));
+    hipLaunchKernelGGL((k_panel_tile<256, 64, true>), dim3((unsigned)((c->m / 256) * (c->n / 64))), dim3(256), 0,
+                       c->stream, p.A, p.lda, c->n, c->at<__bf16>(L.At));
+    LAUNCH_CHECK("k_panel_tile");
+    hipLaunchKernelGGL((k_panel_tile<64, 256, false>), dim3((unsigned)((c->m / 64) * (c->n / 256))), dim3(256), 0,
+                       c->stream, p.A, p.lda, c->n, c->at<__bf16>(L.A1t));
+    LAUNCH_CHECK("k_panel_tile");
     c->masked = false;   // p.W is null again
     panel_fuse_check(c);
     c->bound = true;
@@ -503,10 +491,8 @@ int bpgl_panel_reset(bpgl_panel* c, const double* B, const double* mu, double* e
     PanelParams& p = c->p;
     const int64_t km = (int64_t)c->k * c->m;
     if (c->masked) {   // the stored B is w o B (so R0 = -w o B and A x - B stays masked); (1 - w) o B for the score
-        const PanelLayout L = panel_layout(c);
         hipLaunchKernelGGL(k_panel_mask_b, dim3((unsigned)std::min<int64_t>(cdiv(km, kThreads), 2048)), dim3(kThreads),
-                           0, c->stream, B, p.W, (long long)km, const_cast<double*>(p.B),
-                           (double*)((char*)p.st + (L.Bh - L.st)));
+                           0, c->stream, B, p.W, (long long)km, const_cast<double*>(p.B), c->at<double>(c->L.Bh));
         LAUNCH_CHECK("k_panel_mask_b");
     } else {
         HIP_TRY(hipMemcpyAsync(const_cast<double*>(p.B), B, 8 * km, hipMemcpyDeviceToDevice, c->stream));
@@ -525,7 +511,7 @@ int bpgl_panel_reset(bpgl_panel* c, const double* B, const double* mu, double* e
     HIP_TRY(hipMemsetAsync(p.lsdone, 0, 8, c->stream));
     hipLaunchKernelGGL(k_panel_reset_state, dim3(1), dim3(64), 0, c->stream, c->p);
     LAUNCH_CHECK("k_panel_reset_state");
-    p.Sh = panel_carry(c) ? (__bf16*)((char*)p.st + (panel_layout(c).Sh - panel_layout(c).st)) : nullptr;
+    p.Sh = panel_carry(c) ? c->at<__bf16>(c->L.Sh) : nullptr;
     drop_graphs(c);
     if (use_graph) {
         // kGraphIters iterations; with the carried gradient a second graph whose first iteration is
@@ -583,8 +569,8 @@ int bpgl_panel_step(bpgl_panel* c, int64_t n_iter) {
     }
     if (c->nblock == 1 && c->defer_x) {   // the last iteration's x update, so X is current between calls
         const dim3 fg((unsigned)std::min<int64_t>(cdiv((int64_t)c->k * c->w / 8, kThreads), 8192));
-        if (c->dsplit == 1) hipLaunchKernelGGL(k_panel_flush<1>, fg, dim3(kThreads), 0, c->stream, c->p);
-        else hipLaunchKernelGGL(k_panel_flush<2>, fg, dim3(kThreads), 0, c->stream, c->p);
+        const auto flush = dispatch<1, 2>(c->dsplit, [](auto ds) { return &k_panel_flush<decltype(ds)::value>; });
+        hipLaunchKernelGGL(flush, fg, dim3(kThreads), 0, c->stream, c->p);
         LAUNCH_CHECK("k_panel_flush");
         hipLaunchKernelGGL(k_panel_clear_pending, dim3(1), dim3(64), 0, c->stream, c->p);
         LAUNCH_CHECK("k_panel_clear_pending");
@@ -708,8 +694,7 @@ int bpgl_panel_set_row_mask(bpgl_panel* c, const uint8_t* mask) {
     int rc;
     if ((rc = panel_ready(c))) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    const PanelLayout L = panel_layout(c);
-    unsigned char* W = (unsigned char*)c->p.st + (L.W - L.st);
+    unsigned char* W = c->at<unsigned char>(c->L.W);
     if (mask) HIP_TRY(hipMemcpyAsync(W, mask, (int64_t)c->k * c->m, hipMemcpyDeviceToDevice, c->stream));
     c->masked = mask != nullptr;
     c->p.W = mask ? W : nullptr;
@@ -728,11 +713,10 @@ int bpgl_panel_gap(bpgl_panel* c, double* G_all, double* R_fresh, uint8_t* keep,
     if (((uintptr_t)G_all) % 16 || ((uintptr_t)R_fresh) % 16)
         return fail(BPGL_E_ARG, "G_all and R_fresh must be 16-byte aligned");
     if ((rc = bpgl_panel_status(c, nullptr, nullptr))) return rc;   // waits; reports a failed exchange
-    const PanelLayout L = panel_layout(c);
-    char* s = (char*)c->p.st - L.st;
-    double* parts = (double*)(s + L.gparts);
-    double* res = (double*)(s + L.gres);
-    int* counts = (int*)(s + L.gcounts);
+    const PanelLayout& L = c->L;
+    double* parts = c->at<double>(L.gparts);
+    double* res = c->at<double>(L.gres);
+    int* counts = c->at<int>(L.gcounts);
     PanelGapArgs a{};
     a.A = c->p.A;
     a.lda = c->p.lda;
@@ -748,10 +732,10 @@ int bpgl_panel_gap(bpgl_panel* c, double* G_all, double* R_fresh, uint8_t* keep,
     a.mu = c->p.mu;
     a.Rf = R_fresh;
     a.G = G_all;
-    a.part = (double*)(s + L.gpart);
+    a.part = c->at<double>(L.gpart);
     a.W = c->masked ? c->p.W : nullptr;
-    a.Bh = (const double*)(s + L.Bh);
-    a.hpart = (double*)(s + L.ghold);
+    a.Bh = c->at<double>(L.Bh);
+    a.hpart = c->at<double>(L.ghold);
     for (auto& e : c->gap_ev)
         if (!e) HIP_TRY(hipEventCreate(&e));
     HIP_TRY(hipEventRecord(c->gap_ev[0], c->stream));
