@@ -105,10 +105,14 @@ def stored(A, type_name):
     return b.astype(np.uint32).view(np.float32).astype(np.float64)
 
 
-def instance(m, n, type_name, seed, mu_scale=0.1):
-    """tests/test_onepass.py's recipe: randn / sqrt(n), 30 % support, mu = 0.1 |A^T b|_inf; A as stored."""
+def instance(m, n, type_name, seed, mu_scale=0.1, common=0.0):
+    """tests/test_onepass.py's recipe: randn / sqrt(n), 30 % support, mu = 0.1 |A^T b|_inf; A as stored.
+    ``common``: every column also holds this multiple of one shared randn column (see COMMON)."""
     rs = np.random.RandomState(seed)
-    As = stored(rs.randn(m, n) / np.sqrt(n), type_name)
+    A = rs.randn(m, n)
+    if common:
+        A = A + common * rs.randn(m, 1)
+    As = stored(A / np.sqrt(n), type_name)
     b = As @ np.where(rs.rand(n) < 0.3, rs.randn(n), 0.0) + 0.01 * rs.randn(m)
     mu = mu_scale * float(np.abs(As.T @ b).max())
     return As, b, mu
@@ -373,9 +377,10 @@ def line(stats):
 # tests/test_solver_step_host.py can hold every one of them to test_steps_are_informative and to E's
 # conditions without a GPU.  ``seed`` is m + n unless SEEDS says otherwise.
 # --------------------------------------------------------------------------------------------------
-def case(m, n, ty, Block=1, knobs=(), order_seed=None, x0_seed=None, fail_at=None, world=1, stop=False):
+def case(m, n, ty, Block=1, knobs=(), order_seed=None, x0_seed=None, fail_at=None, world=1, stop=False, target=None):
+    """``target``: BPGL_TARGET_BLOCKS while the context is created (None: the default tiling)"""
     return dict(m=m, n=n, ty=ty, Block=Block, knobs=tuple(knobs), order_seed=order_seed, x0_seed=x0_seed,
-                fail_at=fail_at, world=world, stop=stop)
+                fail_at=fail_at, world=world, stop=stop, target=target)
 
 
 def case_id(c):
@@ -386,11 +391,17 @@ def case_id(c):
     s += "-x0" if c["x0_seed"] is not None else ""
     s += f"-fail{c['fail_at']}" if c["fail_at"] is not None else ""
     s += f"-world{c['world']}" if c["world"] > 1 else ""
+    s += f"-target{c['target']}" if c.get("target") is not None else ""
     return s + ("-stop" if c["stop"] else "")
 
 
 SEEDS = {}
-LDS = [(3, 5, "float"), (4099, 1536, "float"), (2000, 1000, "double"), (1500, 6000, "bf16")]
+# Shapes whose columns share a common component.  With 131139 rows for 32 independent columns A^T A is the
+# identity to 1 / sqrt(m / n): the block iteration converges by a factor ~60 per step, D reaches the rounding
+# floor after 6 steps and the rest of the run is not informative.  One shared column of the same size couples
+# the blocks (condition number ~ n) and all 18 steps stay informative.
+COMMON = {(131139, 32, "float"): 1.0}
+LDS =[(3, 5, "float"), (4099, 1536, "float"), (2000, 1000, "double"), (1500, 6000, "bf16")]
 GRANULE = [(1000, 4100, "float"), (37, 9000, "float"), (777, 3000, "double"), (1500, 10000, "bf16")]
 TAILW = [(300, 30000, "float")]
 GPL2 = [(96, 266340, "float"), (64, 133126, "double"), (64, 399368, "bf16")]
@@ -418,7 +429,7 @@ ALL_CASES = ONEPASS_CASES + TWO_PASS_CASES + FALLBACK_CASES + ROW_SHARD_CASES + 
 def case_problem(c):
     """(As, b, mu, order, x0) of a case: the instance, the block order (None: cyclic) and the start."""
     m, n, ty = c["m"], c["n"], c["ty"]
-    As, b, mu = instance(m, n, ty, SEEDS.get((m, n, ty), m + n))
+    As, b, mu = instance(m, n, ty, SEEDS.get((m, n, ty), m + n), common=COMMON.get((m, n, ty), 0.0))
     order = None if c["order_seed"] is None else np.random.RandomState(c["order_seed"]).randint(
         0, c["Block"], size=T_STEPS).astype(np.int32)
     x0 = None if c["x0_seed"] is None else np.random.RandomState(c["x0_seed"]).randn(n)

@@ -46,10 +46,14 @@ T = S.T_STEPS
 WORST = {}
 
 
-def make_gc(type_name, A, Block, **kw):
+def make_gc(type_name, A, Block, target=None, **kw):
+    """``target``: BPGL_TARGET_BLOCKS, set while the context is created only (it fixes the tiling there)"""
     cls = type("GC_" + type_name, (GPU_Calculation,), {"TYPE": type_name})
-    with warnings.catch_warnings():          # the shared instance is read-only; the upload only reads it
+    with warnings.catch_warnings(), pytest.MonkeyPatch.context() as mp:
+        # the shared instance is read-only; the upload only reads it
         warnings.filterwarnings("ignore", message="The given NumPy array is not writable")
+        if target is not None:
+            mp.setenv("BPGL_TARGET_BLOCKS", str(target))
         return cls(A, Block, device=0, **kw)
 
 
@@ -97,11 +101,15 @@ def expected_form(c, gc):
     return SB, ng, rows, int(gpl_eff == 0)
 
 
-def run_single_rank(c):
+def run_single_rank(c, on_context=None, on_report=None):
+    """``on_context(gc)``: called on the new context (tests/test_twopass_geometry.py asserts its tiling);
+    ``on_report(stats)``: receives the run's worst ratios to bound."""
     As, b, mu, order, x0, bound, t_stop = problem(c)
     m, n, Block = c["m"], c["n"], c["Block"]
     carried = S.case_carried(c)
-    gc = make_gc(c["ty"], As, Block)
+    gc = make_gc(c["ty"], As, Block, target=c.get("target"))
+    if on_context is not None:
+        on_context(gc)
     assert np.array_equal(gc.A_b_gpu.to(torch.float64).cpu().numpy(), np.stack(np.hsplit(As, Block)))
     gc.set_tuning("onepass_refresh", S.REFRESH)
     for k, v in c["knobs"]:
@@ -143,6 +151,8 @@ def run_single_rank(c):
     stats = {}
     bad = S.check_run(As, b, diag, mu, Block, snaps, gammas, errs, carried, order=order, x0=x0, parts=parts,
                       ngroups=ng, exact_from=c["fail_at"], t_stop=t_stop, stats=stats)
+    if on_report is not None:
+        on_report(stats)
     report(c, stats, bad)
 
     # the same iterations in one call: graphs replayed
