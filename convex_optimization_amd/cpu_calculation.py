@@ -19,7 +19,8 @@ New beside them (no counterpart in the reference): ``duality_gap`` and ``gap_saf
 numpy fp64 restatement of the device's optimality certificate and screening rule;
 ``panel_duality_gap``, the same per right-hand side of a panel, and ``mu_grid``, the geometric grid
 of a regularization path; ``kfold_masks``, ``masked_panel_iterate`` and ``masked_duality_gap``, the
-restatement of the panel's row-masked problems (K-fold cross-validation).
+restatement of the panel's row-masked problems (K-fold cross-validation, DESIGN.md section 11);
+``compaction_columns``, the columns a screened panel keeps when it is compacted.
 """
 import numpy as np
 
@@ -206,3 +207,22 @@ def masked_duality_gap(A, b, w, x, mu, diag=None):
     score = scale * np.abs(g) + np.sqrt(dg) * np.sqrt(2.0 * np.maximum(gap, 0.0))
     return dict(primal=primal, dual=dual, gap=gap, scale=scale, gnorm_inf=gn, holdout_sse=float(h @ h),
                 score=score, keep=~(score < mu), g=g, r=r)
+
+
+# ---------------------------------------------------------------------------
+# Compaction of a screened panel.
+# ---------------------------------------------------------------------------
+def compaction_columns(keep_union, q):
+    """Sorted original indices (int64) of the columns a compacted panel keeps: the kept columns of
+    ``keep_union`` (n,) bool -- the union over the panel's right-hand sides of the screen's keep -- padded
+    up to the next multiple of ``q`` (at least ``q``) with the screened columns of smallest index.  A
+    screened column is provably zero at every optimum of the panel, so keeping some is harmless; this
+    rule needs no scores and is deterministic.  ValueError if q <= 0 or n is not a multiple of q."""
+    keep = np.asarray(keep_union).reshape(-1) != 0
+    n, q = keep.size, int(q)
+    if q <= 0 or n % q:
+        raise ValueError(f"q (got {q}) must be positive and divide n = {n}")
+    kept = np.flatnonzero(keep)
+    n_new = max(q, -(-kept.size // q) * q)
+    pads = np.flatnonzero(~keep)[:n_new - kept.size]
+    return np.sort(np.concatenate([kept, pads])).astype(np.int64)

@@ -14,13 +14,14 @@
 //   k_gap_final     one block: folds them in block order -> [primal, dual, gap, scale, ||g||_inf]
 //   k_gap_screen    one thread per column: keep[b w_pad + j] = !(score_j < mu), per-block counts
 //   k_gap_count     one block: n_keep = sum of the counts
-//   k_gather_cols   A_out[i][c] = A(i, cols[c]) for 2-, 4- and 8-byte elements
+//   k_gather_cols   A_out[i][c] = A(i, cols[c]) for 2-, 4- and 8-byte elements (bpgl_gather.h)
 // Every reduction is a fixed-order one (wave_sum / wave_max, then the waves, then the blocks in
 // index order): two calls on the same state return the same bits.  No floating-point atomics.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bpgl_gather.h"
 #include "bpgl_kernels.h"
 
 namespace bpgl {
@@ -137,52 +138,6 @@ __global__ __launch_bounds__(kThreads) void k_gap_count(const int* __restrict__ 
     long long tot = 0;
     for (int k = 0; k < kThreads; ++k) tot += red[k];
     res[5] = (double)tot;
-}
-
-// ---------------------------------------------------------------------------
-// gather: A_out[i * lda_out + c] = A(i, cols[c]), c < n_out; cols[c] is a global column index
-// b w + j (element A + b block_stride + i lda + j); an index outside [0, nblock w) -- -1 by
-// convention -- writes 0, and so do the columns c in [n_out, lda_out).
-// One thread owns 16 bytes of an output row (E = 16 / BYTES consecutive columns) for the rows
-// blockIdx.y, blockIdx.y + gridDim.y, ...: consecutive lanes store consecutive 16-byte pieces of
-// one row, and read increasing addresses of the source row when cols is sorted.
-// ---------------------------------------------------------------------------
-template <int BYTES> struct GatherElem;
-template <> struct GatherElem<2> { using type = uint16_t; };
-template <> struct GatherElem<4> { using type = uint32_t; };
-template <> struct GatherElem<8> { using type = uint64_t; };
-
-struct GatherArgs {
-    const void* A;
-    long long lda, block_stride, w, ncols, m;
-    const int* cols;
-    long long n_out;
-    void* out;
-    long long lda_out;
-};
-
-template <int BYTES>
-__global__ __launch_bounds__(kThreads) void k_gather_cols(GatherArgs a) {
-    using T = typename GatherElem<BYTES>::type;
-    constexpr int E = 16 / BYTES;
-    const long long chunk = (long long)blockIdx.x * kThreads + threadIdx.x;
-    if (chunk >= a.lda_out / E) return;
-    long long off[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const long long c = chunk * E + e;
-        const long long col = c < a.n_out ? (long long)a.cols[c] : -1;
-        const bool ok = col >= 0 && col < a.ncols;
-        off[e] = ok ? (col / a.w) * a.block_stride + col % a.w : -1;
-    }
-    const T* __restrict__ src = reinterpret_cast<const T*>(a.A);
-    T* __restrict__ dst = reinterpret_cast<T*>(a.out) + chunk * E;
-    for (long long i = blockIdx.y; i < a.m; i += gridDim.y) {
-        union { T v[E]; u32x4 q; } o;
-#pragma unroll
-        for (int e = 0; e < E; ++e) o.v[e] = off[e] >= 0 ? src[i * a.lda + off[e]] : (T)0;
-        *reinterpret_cast<u32x4*>(dst + i * a.lda_out) = o.q;
-    }
 }
 
 }  // namespace bpgl

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/bpgl.h"
+#include "bpgl_gather.h"
 #include "bpgl_host.h"
 #include "bpgl_panel.h"
 #include "bpgl_panel_gap.h"
@@ -141,7 +142,10 @@ PanelLayout panel_layout(const bpgl_panel* c) {
     // per-RHS partials, the screen's per-block counts and the results.  Laid out last: nothing before
     // them moves.
     const int64_t sp1 = pgap_split(c->m / kPgTile, c->n / kPgK), sp2 = pgap_split(c->n / kPgTile, c->m / kPgK);
-    L.gpart = k.take(8 * (int64_t)c->k * std::max(sp1 * c->m, sp2 * c->n));
+    // bpgl_panel_reset_x0 with nblock > 1 runs product 1 with nblock x pgap_split(m / 64, w / 32)
+    // block-aligned chunks into the same buffer: it grows only where that exceeds the certificate's need
+    const int64_t spw = c->nblock > 1 ? (int64_t)c->nblock * pgap_split(c->m / kPgTile, c->w / kPgK) : 0;
+    L.gpart = k.take(8 * (int64_t)c->k * std::max(std::max(sp1 * c->m, sp2 * c->n), spw * c->m));
     L.gparts = k.take(8 * (int64_t)kPgPart * pgap_nparts(c) * c->k);
     L.gcounts = k.take(4 * (int64_t)c->k * cdiv(c->n, kThreads));
     L.gres = k.take(8 * (int64_t)kPgRes * c->k);
@@ -310,6 +314,52 @@ int panel_split(bpgl_panel* c, const double* src, int64_t len, int64_t ld, __bf1
 void drop_graphs(bpgl_panel* c) {
     if (c->gexec) { (void)hipGraphExecDestroy(c->gexec); c->gexec = nullptr; }
     if (c->gexec_ref) { (void)hipGraphExecDestroy(c->gexec_ref); c->gexec_ref = nullptr; }
+}
+
+// the certificate's view of the context: what both of its products and bpgl_panel_reset_x0's product 1 read
+PanelGapArgs pgap_args(const bpgl_panel* c) {
+    PanelGapArgs a{};
+    a.A = c->p.A;
+    a.lda = c->p.lda;
+    a.m = c->m;
+    a.n = c->n;
+    a.w = c->w;
+    a.nblock = c->nblock;
+    a.k = c->k;
+    a.X = c->p.X;
+    a.B = c->p.B;
+    a.R = c->p.R;
+    a.diag = c->p.diag;
+    a.mu = c->p.mu;
+    a.part = c->at<double>(c->L.gpart);
+    a.W = c->masked ? c->p.W : nullptr;
+    a.Bh = c->at<double>(c->L.Bh);
+    a.hpart = c->at<double>(c->L.ghold);
+    return a;
+}
+// bpgl_panel_reset_x0: R = A X - B (w o (A X - B) with a row mask) from the stored X through the
+// certificate's product 1, and with nblock > 1 also Ax[b] = A_b x_b
+int panel_warm_residual(bpgl_panel* c) {
+    PanelGapArgs a = pgap_args(c);
+    if (c->nblock == 1) {   // the certificate's own chunking and fold, written to the solver's R
+        a.Rf = c->p.R;
+        a.spl = pgap_split(c->m / kPgTile, c->n / kPgK);
+        a.chunk = c->n / kPgK / a.spl;
+        return pgap_prod<1>(c, a, dim3((unsigned)(c->m / kPgTile * a.spl)));
+    }
+    // chunks aligned to the feature blocks: spb per block, chunk q inside block q / spb
+    const int spb = pgap_split(c->m / kPgTile, c->w / kPgK);
+    a.spl = c->nblock * spb;
+    a.chunk = c->w / kPgK / spb;
+    const dim3 blk(kThreads), grid((unsigned)(c->m / kPgTile * a.spl));
+    const auto prod = dispatch_nt(c->k, [](auto nt) { return &k_pgap_prod<decltype(nt)::value, 1>; });
+    hipLaunchKernelGGL(prod, grid, blk, 0, c->stream, a);
+    LAUNCH_CHECK("k_pgap_prod");
+    const dim3 fgrid((unsigned)cdiv((int64_t)c->k * c->m, kThreads));
+    if (c->masked) hipLaunchKernelGGL(k_pgap_fold_ax<true>, fgrid, blk, 0, c->stream, a, spb, c->p.Ax, c->p.R);
+    else hipLaunchKernelGGL(k_pgap_fold_ax<false>, fgrid, blk, 0, c->stream, a, spb, c->p.Ax, c->p.R);
+    LAUNCH_CHECK("k_pgap_fold_ax");
+    return 0;
 }
 
 int panel_ready(const bpgl_panel* c) {
@@ -483,10 +533,16 @@ int bpgl_panel_mm(bpgl_panel* c, int32_t block, const double* D, double* S) {
 
 int bpgl_panel_reset(bpgl_panel* c, const double* B, const double* mu, double* err_iter, int64_t record_len,
                      int use_graph) {
+    return bpgl_panel_reset_x0(c, B, mu, nullptr, err_iter, record_len, use_graph);
+}
+
+int bpgl_panel_reset_x0(bpgl_panel* c, const double* B, const double* mu, const float* X0, double* err_iter,
+                        int64_t record_len, int use_graph) {
     int rc;
     if ((rc = panel_ready(c))) return rc;
     if (!c->have_diag) return fail(BPGL_E_STATE, "bpgl_panel_diag must run before the solver");
     if (!B || !mu) return fail(BPGL_E_ARG, "B and mu must be non-null");
+    if (((uintptr_t)X0) % 16) return fail(BPGL_E_ARG, "X0 must be 16-byte aligned");
     HIP_TRY(hipSetDevice(c->device));
     PanelParams& p = c->p;
     const int64_t km = (int64_t)c->k * c->m;
@@ -498,10 +554,19 @@ int bpgl_panel_reset(bpgl_panel* c, const double* B, const double* mu, double* e
         HIP_TRY(hipMemcpyAsync(const_cast<double*>(p.B), B, 8 * km, hipMemcpyDeviceToDevice, c->stream));
     }
     HIP_TRY(hipMemcpyAsync(const_cast<double*>(p.mu), mu, 8 * c->k, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(p.X, 0, 4 * (int64_t)c->k * c->w * c->nblock, c->stream));
-    HIP_TRY(hipMemsetAsync(p.Ax, 0, 8 * km * c->nblock, c->stream));
-    // x = 0 => Ax = 0, R = -B
-    if ((rc = panel_split(c, p.B, c->m, c->ldr(), p.Rh, p.Rl, -1.0, p.R))) return rc;
+    const int64_t xbytes = 4 * (int64_t)c->k * c->w * c->nblock;
+    if (!X0) {
+        HIP_TRY(hipMemsetAsync(p.X, 0, xbytes, c->stream));
+        HIP_TRY(hipMemsetAsync(p.Ax, 0, 8 * km * c->nblock, c->stream));
+        // x = 0 => Ax = 0, R = -B
+        if ((rc = panel_split(c, p.B, c->m, c->ldr(), p.Rh, p.Rl, -1.0, p.R))) return rc;
+    } else {
+        // x = X0 (the stored iterate itself when X0 is bpgl_panel_x), R = A x - B and Ax from the fp64
+        // product on that fp32 x, R's images from that R
+        if (X0 != p.X) HIP_TRY(hipMemcpyAsync(p.X, X0, xbytes, hipMemcpyDeviceToDevice, c->stream));
+        if ((rc = panel_warm_residual(c))) return rc;
+        if ((rc = panel_split(c, p.R, c->m, c->ldr(), p.Rh, p.Rl, 1.0, nullptr))) return rc;
+    }
     c->t_host = 0;
     c->n_exact = 0;
     p.err_iter = err_iter;
@@ -717,25 +782,9 @@ int bpgl_panel_gap(bpgl_panel* c, double* G_all, double* R_fresh, uint8_t* keep,
     double* parts = c->at<double>(L.gparts);
     double* res = c->at<double>(L.gres);
     int* counts = c->at<int>(L.gcounts);
-    PanelGapArgs a{};
-    a.A = c->p.A;
-    a.lda = c->p.lda;
-    a.m = c->m;
-    a.n = c->n;
-    a.w = c->w;
-    a.nblock = c->nblock;
-    a.k = c->k;
-    a.X = c->p.X;
-    a.B = c->p.B;
-    a.R = c->p.R;
-    a.diag = c->p.diag;
-    a.mu = c->p.mu;
+    PanelGapArgs a = pgap_args(c);
     a.Rf = R_fresh;
     a.G = G_all;
-    a.part = c->at<double>(L.gpart);
-    a.W = c->masked ? c->p.W : nullptr;
-    a.Bh = c->at<double>(L.Bh);
-    a.hpart = c->at<double>(L.ghold);
     for (auto& e : c->gap_ev)
         if (!e) HIP_TRY(hipEventCreate(&e));
     HIP_TRY(hipEventRecord(c->gap_ev[0], c->stream));
@@ -777,6 +826,32 @@ int bpgl_panel_gap(bpgl_panel* c, double* G_all, double* R_fresh, uint8_t* keep,
     }
     if (!keep)
         for (int k = 0; k < c->k; ++k) out[(int64_t)k * kPgRes + 5] = (double)c->n;
+    return 0;
+}
+
+int bpgl_panel_gather_columns(bpgl_panel* c, const int32_t* cols, int64_t n_out, void* A_out, int64_t lda_out) {
+    int rc;
+    if ((rc = panel_ready(c))) return rc;
+    if (!cols || !A_out) return fail(BPGL_E_ARG, "cols and A_out must be non-null");
+    constexpr int V = 8;   // bf16 elements of a 16-byte piece
+    if (n_out <= 0) return fail(BPGL_E_ARG, "n_out must be > 0");
+    if (lda_out < n_out || lda_out % V)
+        return fail(BPGL_E_ARG, "lda_out (%lld) must be >= n_out (%lld) and a multiple of %d", (long long)lda_out,
+                    (long long)n_out, V);
+    if (((uintptr_t)A_out) % 16) return fail(BPGL_E_ARG, "A_out must be 16-byte aligned");
+    if (lda_out / V > (int64_t)0x7fffffff * kThreads) return fail(BPGL_E_ARG, "lda_out too large");
+    {   // A_out [m][lda_out] against the bound A [m][lda]
+        const uintptr_t a0 = (uintptr_t)c->p.A, a1 = a0 + 2 * (uintptr_t)((c->m - 1) * c->p.lda + c->n);
+        const uintptr_t o0 = (uintptr_t)A_out, o1 = o0 + 2 * (uintptr_t)(c->m * lda_out);
+        if (o0 < a1 && a0 < o1) return fail(BPGL_E_ARG, "A_out overlaps the bound A");
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    GatherArgs a{c->p.A, c->p.lda, 0, c->n, c->n, c->m, cols, n_out, A_out, lda_out};
+    const int64_t gx = cdiv(lda_out / V, kThreads);
+    // about 4096 blocks; each thread walks rows blockIdx.y, + gridDim.y, ... with its column offsets in registers
+    const int64_t gy = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(c->m, 65535), cdiv(4096, gx)));
+    hipLaunchKernelGGL(k_gather_cols<2>, dim3((unsigned)gx, (unsigned)gy), dim3(kThreads), 0, c->stream, a);
+    LAUNCH_CHECK("k_gather_cols");
     return 0;
 }
 

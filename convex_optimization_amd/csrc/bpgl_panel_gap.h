@@ -30,6 +30,9 @@
 // order, 4 at a time through the MFMA; then the chunks; then wave_sum / wave_max, the waves, the
 // blocks in index order).  No floating-point atomics: two calls on the same state return the same
 // bits.
+// bpgl_panel_reset_x0 runs product 1 on X0 into the solver's R: with one feature
+// block through k_pgap_fold<1> as above, with more through
+//   k_pgap_fold_ax          Ax[b] = block b's chunks (the chunks aligned to the blocks), R = sum_b Ax[b] - B
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -211,6 +214,31 @@ __global__ __launch_bounds__(kThreads) void k_pgap_fold(PanelGapArgs a) {
         if (PROD == 1) a.Rf[e] = v - a.B[e];
         else a.G[((o / a.w) * a.k + k) * a.w + o % a.w] = v;
     }
+}
+
+// bpgl_panel_reset_x0 with more than one feature block: product 1 ran with its
+// chunks aligned to the feature blocks (a.spl = nblock x spb, chunk c inside block c / spb).  One thread
+// per (rhs, row): Ax[b] = block b's chunks added in chunk order, R = sum_b Ax[b] - B with b in index
+// order, as k_panel_update sums them.  MK (a.B holds w o B): Ax[b] and R are 0 at the held-out rows,
+// by select -- the solver's Ax is the sum of masked S, so it is masked too.
+template <bool MK>
+__global__ __launch_bounds__(kThreads) void k_pgap_fold_ax(PanelGapArgs a, int spb, double* __restrict__ Ax,
+                                                           double* __restrict__ R) {
+    const long long e = (long long)blockIdx.x * kThreads + threadIdx.x;
+    const long long km = (long long)a.k * a.m;
+    if (e >= km) return;
+    bool in = true;
+    if constexpr (MK) in = a.W[e] != 0;
+    double acc = 0.0;
+    for (int b = 0; b < a.nblock; ++b) {
+        const double* part = a.part + (long long)b * spb * km + e;
+        double v = part[0];
+        for (int c = 1; c < spb; ++c) v += part[(long long)c * km];
+        v = in ? v : 0.0;
+        Ax[(long long)b * km + e] = v;
+        acc = b == 0 ? v : acc + v;
+    }
+    R[e] = in ? acc - a.B[e] : 0.0;
 }
 
 // one block per RHS: res[k][7] = the held-out partials of its nb fold blocks, thread q taking blocks

@@ -32,11 +32,15 @@ the bf16 A), and ``lasso_path`` runs one b against a grid 
 with that certificate as its stopping rule.  ``PanelLasso.set_row_mask`` gives every right-hand side
 0/1 row weights, and ``lasso_cv`` uses them to run K-fold cross-validation over a grid of mu as one
 panel (K folds x J values of mu = K J columns on one bound A).
+``PanelLasso.solver_reset(x0=...)`` starts the panel at a given x and ``gather_columns`` compacts the
+bound A; ``lasso_path`` and ``lasso_cv`` use them, opt-in, to warm-start and to drop columns the
+gap-safe screen proves zero for every right-hand side.
 
 All compute goes through libbpgl.so (bpgl_panel_* in include/bpgl.h).
 """
 import contextlib
 import ctypes
+import time
 
 import numpy as np
 import torch
@@ -67,6 +71,8 @@ _PANEL_SIGS = {
     "bpgl_panel_residual": (_p, [_p]),
     "bpgl_panel_gap": (ctypes.c_int, [_p, _p, _p, _p, ctypes.POINTER(ctypes.c_double)]),
     "bpgl_panel_set_row_mask": (ctypes.c_int, [_p, _p]),
+    "bpgl_panel_reset_x0": (ctypes.c_int, [_p, _p, _p, _p, _p, _i64, ctypes.c_int]),
+    "bpgl_panel_gather_columns": (ctypes.c_int, [_p, _p, _i64, _p, _i64]),
 }
 N._SIGS.update(_PANEL_SIGS)
 
@@ -183,16 +189,57 @@ class PanelLasso:
             out = S.t().contiguous()
         return out
 
-    def solver_reset(self, B, mu, record_len=0, use_graph=True):
-        """B (m, k) right-hand sides, mu scalar or (k,)."""
+    def _x0_layout(self, x0):
+        """x0, (n, k) or the (k, n) of ``solver_x_device`` -> (device fp32 tensor [nblock][k][w], its address);
+        the stored iterate itself (one feature block: ``solver_x_device()`` is a view of it) is passed on
+        as it is, and bpgl_panel_reset_x0 then copies nothing."""
+        k, n = self.nrhs, self.MAT_WIDTH_ALL
+        t = x0 if isinstance(x0, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x0))
+        if tuple(t.shape) == (n, k):
+            t = t.t()
+        elif tuple(t.shape) != (k, n):
+            raise ValueError(f"x0 must be (n, k) = ({n}, {k}), got {tuple(t.shape)}")
+        if t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and self.Block == 1 \
+                and t.data_ptr() == _lib().bpgl_panel_x(self._ctx):
+            return t, t.data_ptr()
+        t = t.to(device=self.device, dtype=torch.float32)
+        t = t.reshape(k, self.Block, self.MAT_WIDTH).permute(1, 0, 2).contiguous()
+        return t, t.data_ptr()
+
+    def solver_reset(self, B, mu, record_len=0, use_graph=True, x0=None):
+        """B (m, k) right-hand sides, mu scalar or (k,).  ``x0``: None starts at x = 0 (bpgl_panel_reset);
+        an (n, k) array or tensor (or the (k, n) of ``solver_x_device``) starts at its fp32 rounding
+        (bpgl_panel_reset_x0: R = A x0 - B from the certificate's fp64 product; include/bpgl.h).
+        ``solver_x_device()`` of this context (one feature block) restarts from the stored iterate
+        without a copy."""
         with self._on_stream():
             self._Bt = self._dev(B, (self.MAT_HEIGHT, self.nrhs)).t().contiguous()
             mu_v = np.broadcast_to(np.asarray(mu, dtype=np.float64), (self.nrhs,)).copy()
             self._mu = torch.from_numpy(mu_v).to(self.device)
             self._err_iter = torch.zeros(max(1, record_len), dtype=torch.float64, device=self.device) \
                 if record_len else None
-            N.check(_lib().bpgl_panel_reset(self._ctx, N.ptr(self._Bt), N.ptr(self._mu), N.ptr(self._err_iter),
-                                            int(record_len), int(bool(use_graph))), "bpgl_panel_reset")
+            if x0 is None:
+                N.check(_lib().bpgl_panel_reset(self._ctx, N.ptr(self._Bt), N.ptr(self._mu), N.ptr(self._err_iter),
+                                                int(record_len), int(bool(use_graph))), "bpgl_panel_reset")
+            else:
+                self._x0, addr = self._x0_layout(x0)   # kept: the copy is enqueued, not done
+                N.check(_lib().bpgl_panel_reset_x0(self._ctx, N.ptr(self._Bt), N.ptr(self._mu), ctypes.c_void_p(addr),
+                                                   N.ptr(self._err_iter), int(record_len), int(bool(use_graph))),
+                        "bpgl_panel_reset_x0")
+
+    def gather_columns(self, cols):
+        """(m, lda_out) bf16 device tensor with column c = column cols[c] of the stored A
+        (bpgl_panel_gather_columns): ``cols`` int array or tensor in any order, an index outside [0, n)
+        gives a zero column; lda_out = len(cols) rounded up to 8, the pad columns zero."""
+        with self._on_stream():
+            t = cols if isinstance(cols, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(cols))
+            t = t.reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
+            n_out = int(t.numel())
+            lda_out = -(-n_out // 8) * 8
+            out = torch.empty((self.MAT_HEIGHT, lda_out), dtype=torch.bfloat16, device=self.device)
+            N.check(_lib().bpgl_panel_gather_columns(self._ctx, N.ptr(t), n_out, N.ptr(out), lda_out),
+                    "bpgl_panel_gather_columns")
+        return out
 
     def set_row_mask(self, mask):
         """0/1 row weights per right-hand side: ``mask`` (m, k) bool / uint8 array or tensor, nonzero =
@@ -351,8 +398,75 @@ def _check_loop(pl, target, ITER_MAX, check_every):
     return t, cert, first
 
 
+def _check_shrink(shrink):
+    if not 0.0 <= float(shrink) < 1.0:
+        raise ValueError("shrink must lie in [0, 1)")
+    return float(shrink)
+
+
+def _screened_loop(pl, B, mu, target, ITER_MAX, check_every, shrink, mask=None):
+    """``_check_loop`` on a freshly reset ``pl`` (reset with ``B``, ``mu``; ``mask``: the (m, k) row mask
+    installed on it, or None) with gap-safe compaction, ``ClassLassoScreened``'s rule on a panel: after
+    a check that did not stop the loop, the union over the panel's columns of the screen's keep goes
+    through ``cpu_calculation.compaction_columns`` with q = Block * 256; when that leaves at most
+    ``shrink`` times the active columns, they are gathered (``gather_columns``), a new ``PanelLasso`` of
+    the same Block and width is built over them, the mask installed there, and the solve continues
+    from ``solver_reset(B, mu, x0=X[sel])``.  ``pl`` stays alive; an earlier narrow context is dropped.
+
+    Returns dict(t, cert, first, reached, x (n, k), active, compactions [(t, n_active after)],
+    compact_seconds).  ``reached`` is the loop's own verdict.  After a compaction ``cert`` is one
+    ``duality_gap(screen=False)`` on ``pl`` itself, reset (mask still installed) at x scattered back
+    to (n, k) with zeros outside ``active``: the dropped columns need not be dual-feasible for the
+    compacted problem's dual point.  ``shrink=0`` is ``_check_loop`` and ``pl.solver_x()``, nothing else."""
+    from .cpu_calculation import compaction_columns
+    n, k = pl.MAT_WIDTH_ALL, pl.nrhs
+    active = np.arange(n, dtype=np.int64)
+    if shrink == 0.0:
+        t, cert, first = _check_loop(pl, target, ITER_MAX, check_every)
+        return dict(t=t, cert=cert, first=first, reached=cert["gap"] <= target, x=pl.solver_x(), active=active,
+                    compactions=[], compact_seconds=0.0)
+    q = pl.Block * 256
+    first = np.full(k, -1, dtype=np.int64)
+    cur, t, cert, compactions, seconds = pl, 0, None, [], 0.0
+    while t < int(ITER_MAX):
+        step = min(int(check_every), int(ITER_MAX) - t)
+        cur.solver_step(step)
+        t += step
+        cert = cur.duality_gap(screen=True)
+        ok = cert["gap"] <= target
+        first[ok & (first < 0)] = t
+        if ok.all() or t >= int(ITER_MAX):
+            break
+        sel = compaction_columns(cert["keep"].any(dim=0).cpu().numpy(), q)
+        if sel.size <= shrink * active.size:
+            t0 = time.time()
+            sel_d = torch.from_numpy(sel).to(cur.device)
+            x0 = cur.solver_x_device()[:, sel_d].clone()          # (k, n_new) fp32
+            nxt = PanelLasso(cur.gather_columns(sel_d), pl.Block, nrhs=k, device=pl.device)
+            if mask is not None:
+                nxt.set_row_mask(mask)
+            nxt.solver_reset(B, mu, x0=x0)
+            nxt.stream.synchronize()
+            cur, active = nxt, active[sel]                        # a narrow `cur` is released here
+            compactions.append((t, int(active.size)))
+            seconds += time.time() - t0
+    if cert is None:
+        cert = cur.duality_gap(screen=True)
+    reached = cert["gap"] <= target
+    x = cur.solver_x()
+    if compactions:
+        x_full = np.zeros((n, k))
+        x_full[active] = x
+        x = x_full
+        del cur
+        pl.solver_reset(B, mu, use_graph=False, x0=x)
+        cert = pl.duality_gap(screen=False)
+    return dict(t=t, cert=cert, first=first, reached=reached, x=x, active=active, compactions=compactions,
+                compact_seconds=seconds)
+
+
 def lasso_path(A, b, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_BOUND=1e-4, ITER_MAX=4096,
-               check_every=PATH_CHECK_EVERY, device=None):
+               check_every=PATH_CHECK_EVERY, device=None, x0=None, shrink=0.0):
     """A regularization path as ONE panel: min 1/2 ||A x - b||^2 + mu ||x||_1 for every mu of a grid,
     on the bf16-stored A, every column of the panel holding the same b.
 
@@ -363,17 +477,32 @@ def lasso_path(A, b, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_BOUND=1e-4
 
     The loop runs ``check_every`` iterations (block updates), then ``PanelLasso.duality_gap``; it
     stops at the first check where every mu has gap <= GAP_BOUND * 1/2 ||b||^2 (ClassLassoScreened's
-    criterion), or after ITER_MAX iterations.  No compaction and no warm start: every mu starts at
-    x = 0 and runs until the slowest is done.  GAP_BOUND below about 1e-6 is out of reach of the fp32
-    x.
+    criterion), or after ITER_MAX iterations; all mu run until the slowest is done.  GAP_BOUND below
+    about 1e-6 is out of reach of the fp32 x.
+
+    By default every mu starts at x = 0 and the panel keeps its width.  Opt-in:
+    ``x0``, an (n, len(mus)) array, starts every mu at the given point (only with ``mus`` given,
+    ValueError otherwise; the pad columns take the column of the largest mu).  ``shrink`` in [0, 1)
+    (ValueError outside) compacts the panel as it runs (``_screened_loop``); 0 disables it.
 
     Returns a dict: x (n, len(mus)), mus, mu_max (None when mus was given), iters, reached (bool per
     mu), first_reached (the iteration of the first check at which that mu met the bound, else -1), and
-    the last certificate's primal, dual, gap, scale, gnorm_inf, n_keep, drift per mu."""
+    the last certificate's primal, dual, gap, scale, gnorm_inf, n_keep, drift per mu (after a
+    compaction: of the final x on the full A, n_keep = n); active (the original indices still active
+    at the end, arange(n) without compaction), compactions (a list of (t, n_active after)) and
+    compact_seconds (gather, the new context, its reset and graph capture)."""
     from .cpu_calculation import mu_grid
     if int(check_every) <= 0:
         raise ValueError("check_every must be > 0")
+    shrink = _check_shrink(shrink)
+    if x0 is not None and mus is None:
+        raise ValueError("x0 needs mus: the grid the columns of x0 belong to")
     b = np.asarray(b.detach().cpu() if isinstance(b, torch.Tensor) else b, dtype=np.float64).reshape(-1)
+    if x0 is not None:
+        x0 = np.asarray(x0.detach().cpu() if isinstance(x0, torch.Tensor) else x0, dtype=np.float64)
+        want = (int(A.shape[1]), int(np.asarray(mus).size))
+        if x0.shape != want:
+            raise ValueError(f"x0 must be (n, len(mus)) = {want}, got {x0.shape}")
     if mus is None:
         if not 1 <= int(n_mus) <= PANEL_NRHS[-1]:
             raise ValueError(f"lasso_path takes 1 to {PANEL_NRHS[-1]} values of mu (got {n_mus})")
@@ -389,18 +518,25 @@ def lasso_path(A, b, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_BOUND=1e-4
         pl.solver_reset(B, 1.0)
         mu_max = float(pl.duality_gap(screen=False)["gnorm_inf"][0])
         grid, _ = pad_mus(mu_grid(mu_max, n_given, hi, lo))
-    pl.solver_reset(B, grid)
+    if x0 is None:
+        pl.solver_reset(B, grid)
+    else:
+        pad = np.repeat(x0[:, [int(np.argmax(grid[:n_given]))]], k - n_given, axis=1)
+        pl.solver_reset(B, grid, x0=np.concatenate([x0, pad], axis=1))
     target = float(GAP_BOUND) * 0.5 * float(b @ b)
-    t, cert, first = _check_loop(pl, target, ITER_MAX, check_every)
-    out = dict(x=pl.solver_x()[:, :n_given], mus=grid[:n_given].copy(), mu_max=mu_max, iters=t,
-               reached=(cert["gap"] <= target)[:n_given], first_reached=first[:n_given])
+    run = _screened_loop(pl, B, grid, target, ITER_MAX, check_every, shrink)
+    cert = run["cert"]
+    out = dict(x=run["x"][:, :n_given], mus=grid[:n_given].copy(), mu_max=mu_max, iters=run["t"],
+               reached=run["reached"][:n_given], first_reached=run["first"][:n_given])
     for key in PanelLasso.GAP_KEYS:
         out[key] = cert[key][:n_given]
+    out.update(active=run["active"], compactions=run["compactions"], compact_seconds=run["compact_seconds"])
     return out
 
 
 def lasso_cv(A, b, n_folds=8, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_BOUND=1e-4, ITER_MAX=4096,
-             check_every=PATH_CHECK_EVERY, seed=0, masks=None, refit=True, return_x=False, device=None):
+             check_every=PATH_CHECK_EVERY, seed=0, masks=None, refit=True, return_x=False, device=None,
+             shrink=0.0, warm_refit=False):
     """K-fold cross-validation over a grid of mu as ONE panel on one bound A: column c = f * n_mus + j
     solves fold f (the rows of ``masks[f]``) at ``mus[j]``, min 1/2 ||w_f o (A x - b)||^2 + mu_j ||x||_1,
     through ``PanelLasso.set_row_mask``.  n_folds * n_mus <= 128 and n_folds >= 2 (ValueError
@@ -421,10 +557,17 @@ def lasso_cv(A, b, n_folds=8, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_B
     and n_keep (n_folds, n_mus) from the last certificate; masks.  ``return_x``: also x_folds
     (n, n_folds, n_mus).  ``refit``: the mask is cleared on the SAME context (A stays bound) and the
     full-data path on the grid is solved by the same loop, as ``lasso_path`` pads and stops it: x
-    (n, n_mus), refit_gap (n_mus,) and refit_iters."""
+    (n, n_mus), refit_gap (n_mus,) and refit_iters.
+
+    Opt-in: ``shrink`` in [0, 1) compacts the panel as ``lasso_path`` does, in the
+    fold solve and in the refit, the mask installed on every narrower context; mse, gap and n_keep then
+    come from the certificate of the final x on the full A.  Also returned: active, compactions,
+    compact_seconds of the fold solve (and refit_compactions).  ``warm_refit``: the refit starts each mu
+    from the mean over folds of that mu's fold solutions instead of from 0."""
     from .cpu_calculation import kfold_masks, mu_grid
     if int(check_every) <= 0:
         raise ValueError("check_every must be > 0")
+    shrink = _check_shrink(shrink)
     b = np.asarray(b.detach().cpu() if isinstance(b, torch.Tensor) else b, dtype=np.float64).reshape(-1)
     m = b.size
     if masks is not None:
@@ -455,7 +598,9 @@ def lasso_cv(A, b, n_folds=8, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_B
     pl.set_row_mask(masks[fold].T)
     pl.solver_reset(B, mus[jmu])
     bb = np.array([float((masks[f] * b) @ (masks[f] * b)) for f in range(n_folds)])
-    t, cert, _ = _check_loop(pl, float(GAP_BOUND) * 0.5 * bb[fold], ITER_MAX, check_every)
+    run = _screened_loop(pl, B, mus[jmu], float(GAP_BOUND) * 0.5 * bb[fold], ITER_MAX, check_every, shrink,
+                         mask=masks[fold].T)
+    t, cert = run["t"], run["cert"]
     shape = (n_folds, n_mus)
     count = (masks == 0).sum(axis=1).astype(np.float64)
     mse = cert["holdout_sse"][:ncol].reshape(shape) / count[:, None]
@@ -465,14 +610,21 @@ def lasso_cv(A, b, n_folds=8, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_B
     within = np.flatnonzero(mean_mse <= mean_mse[best] + se_mse[best])
     out = dict(mus=mus.copy(), mse=mse, mean_mse=mean_mse, se_mse=se_mse, best=best,
                best_1se=int(within[np.argmax(mus[within])]), iters=t,
-               reached=(cert["gap"] <= float(GAP_BOUND) * 0.5 * bb[fold])[:ncol].reshape(shape),
-               gap=cert["gap"][:ncol].reshape(shape), n_keep=cert["n_keep"][:ncol].reshape(shape), masks=masks)
+               reached=run["reached"][:ncol].reshape(shape),
+               gap=cert["gap"][:ncol].reshape(shape), n_keep=cert["n_keep"][:ncol].reshape(shape), masks=masks,
+               active=run["active"], compactions=run["compactions"], compact_seconds=run["compact_seconds"])
     if return_x:
-        out["x_folds"] = pl.solver_x()[:, :ncol].reshape(-1, n_folds, n_mus)
+        out["x_folds"] = run["x"][:, :ncol].reshape(-1, n_folds, n_mus)
     if refit:
         grid = np.concatenate([mus, np.full(k - n_mus, mus.max())])   # pad_mus' layout at this panel's width
         pl.set_row_mask(None)
-        pl.solver_reset(B, grid)
-        rt, rcert, _ = _check_loop(pl, float(GAP_BOUND) * 0.5 * float(b @ b), ITER_MAX, check_every)
-        out.update(x=pl.solver_x()[:, :n_mus], refit_gap=rcert["gap"][:n_mus], refit_iters=rt)
+        if warm_refit:   # each mu from the mean of its fold solutions; the pad takes the largest mu's column
+            xm = run["x"][:, :ncol].reshape(-1, n_folds, n_mus).mean(axis=1)
+            xm = np.concatenate([xm, np.repeat(xm[:, [int(np.argmax(mus))]], k - n_mus, axis=1)], axis=1)
+            pl.solver_reset(B, grid, x0=xm)
+        else:
+            pl.solver_reset(B, grid)
+        rrun = _screened_loop(pl, B, grid, float(GAP_BOUND) * 0.5 * float(b @ b), ITER_MAX, check_every, shrink)
+        out.update(x=rrun["x"][:, :n_mus], refit_gap=rrun["cert"]["gap"][:n_mus], refit_iters=rrun["t"],
+                   refit_compactions=rrun["compactions"])
     return out

@@ -79,7 +79,12 @@ const char* bpgl_last_error(void);
  *                squares with a mask installed (0 without, as before); bpgl_panel_scratch_bytes grows
  *                by the mask, the held-out part of B and the certificate's held-out partials.
  *                Measured at 8192 x 65536, nrhs 128: 0.3774 ms per masked iteration against 0.3771
- *                unmasked (inside the run-to-run spread); the unmasked kernels are unchanged. */
+ *                unmasked (inside the run-to-run spread); the unmasked kernels are unchanged.
+ *   306 (0.3.6): + bpgl_panel_reset_x0 (the panel solver started at a given x: R = A x - B from the
+ *                certificate's fp64 product 1) and bpgl_panel_gather_columns (a column-compacted copy
+ *                of the bound A); bpgl_panel_reset is bpgl_panel_reset_x0 with X0 = NULL, bit for bit
+ *                as before.  bpgl_panel_scratch_bytes grows only for nblock > 1 where the product's
+ *                block-aligned chunks need more than the certificate's partials (see below). */
 int bpgl_version(void);
 
 /*
@@ -488,6 +493,40 @@ int bpgl_panel_gap(bpgl_panel* ctx, double* G_all, double* R_fresh, uint8_t* kee
  * fused update's occupancy check is repeated for the variant that will run.
  */
 int bpgl_panel_set_row_mask(bpgl_panel* ctx, const uint8_t* mask);
+/*
+ * Warm start (since ABI 306): bpgl_panel_reset at a given iterate.
+ * X0: device fp32 [nblock][nrhs][w] (the layout of bpgl_panel_x), 16-byte aligned, caller-owned.
+ *   NULL is bpgl_panel_reset exactly (that function is this one with X0 = NULL).  X0 == bpgl_panel_x(ctx)
+ *   is legal and means "restart from the stored iterate": nothing is copied.
+ * After the call the state is that of a fresh reset at X0: X = X0 bitwise; R = A X0 - B in fp64 from the
+ * stored fp32 x and the bf16 A widened exactly -- bpgl_panel_gap's product 1 (the same kernel, reading
+ * the caller's row-major A), never bpgl_panel_mm, whose hi + lo bf16 operand would round x to 16 bits;
+ * Rh / Rl are that R's images.  With a row mask R = w o (A X0 - B), exactly 0 at held-out rows (by
+ * select), and B is stored as bpgl_panel_reset stores it.  With nblock > 1 the product's reduction
+ * chunks are aligned to the feature blocks and a fold writes Ax[b] = A_b x_b (its chunks in chunk
+ * order) and R = sum_b Ax[b] - B with b in index order, as the update kernel sums them; with
+ * nblock == 1 the chunking and the fold are the certificate's own, so a bpgl_panel_gap right after the
+ * call reports drift 0.  The iteration and exact-gradient counters, the arrival counters, the pending
+ * x update, the carried operand and error-feedback state, err_iter and the graphs are as
+ * bpgl_panel_reset leaves them: the first iteration computes the gradient exactly from Rh / Rl.
+ * Scratch: the chunk partials go into bpgl_panel_gap's buffer.  With nblock == 1 that buffer is
+ * unchanged; with nblock > 1 it is the larger of the certificate's need and nrhs x nblock x
+ * pgap_split(m / 64, w / 32) x m doubles, so bpgl_panel_scratch_bytes can be larger than under ABI 305
+ * for such shapes (e.g. nblock not a power of two) and is the same for all others.
+ * Cost over a plain reset: one product 1 (m n nrhs fp64 multiply-adds).  The new kernels contain no
+ * inter-block waits.  Errors as bpgl_panel_reset, plus BPGL_E_ARG for a misaligned X0.
+ */
+int bpgl_panel_reset_x0(bpgl_panel* ctx, const double* B, const double* mu, const float* X0,
+                        double* err_iter, int64_t record_len, int use_graph);
+/*
+ * Column gather of the bound A (since ABI 306): A_out[i * lda_out + c] = A[i][cols[c]] in bf16, read
+ * from the row-major A given to bpgl_panel_bind.  cols: device int32, any order; an index outside
+ * [0, n) writes 0, as do the columns c in [n_out, lda_out).  lda_out >= n_out and a multiple of 8;
+ * A_out is 16-byte aligned and does not overlap A.  Enqueued on the context's stream (the kernel is
+ * bpgl_gather_columns').  BPGL_E_STATE before bpgl_panel_bind, BPGL_E_ARG on bad arguments.
+ */
+int bpgl_panel_gather_columns(bpgl_panel* ctx, const int32_t* cols, int64_t n_out, void* A_out,
+                              int64_t lda_out);
 
 #ifdef __cplusplus
 }
