@@ -73,16 +73,13 @@ struct bpgl_ctx {
     // replays the largest that fits (one replay gap per graph, not per 8 iterations)
     hipGraphExec_t gexec[kGraphLevels] = {};
     int graph_max = kGraphMaxIters;   // "graph_max" knob (RCCL contexts cap it at kGraphIters)
-    // timing
-    bool timing = false;
-    std::vector<hipEvent_t> evs;   // 2 events per (timed iteration, kind)
-    std::vector<hipEvent_t> ref_evs;   // 2 events per timed exact-gradient refresh (kind 8)
-    int64_t ref_timed = 0;
-    int64_t timed_iters = 0;
-    bool kind_used[kTimedKinds] = {};
+    // timing.  kinds: 0 colpass, 1 shrink, 2 rowpass, 3 rowreduce, 4 allreduce, 5 step, 6 update, 7 onepass;
+    // kind 8 (the exact-gradient refresh, not in every iteration) has its own events, 2 per refresh
+    KernelTimes<kTimedKinds - 1> tm;
+    KernelTimes<1> ref_tm;
     double wall_tick_s = 1e-8;
     int reverse_rows = 0;
-    int col_mode = 1;      // k_colpass row schedule (see launch_colpass)
+    int col_mode = 1;      // k_colpass row schedule (see colpass)
     int nt_loads = 1;
     int tail_permille = 120;
     // one-pass iteration (bpgl_onepass.h)
@@ -201,6 +198,15 @@ int op_rows_eff(const bpgl_ctx* c) {
     if (c->op_rows >= 0) return c->op_rows;
     return c->op_SB >= 16 && c->op_ngroups >= 8 && c->op_R >= 128 ? 1 : 0;
 }
+// The kernels' copies (Params, OnePassArgs) of knob values.  bpgl_bind and every change of a knob call
+// this; nothing else writes these fields.
+void knob_mirrors(bpgl_ctx* c) {
+    c->p.reverse_rows = c->reverse_rows;
+    c->p.tail_permille = c->tail_permille;
+    c->op.cache_permille = op_cache_eff(c);
+    if (c->op_shape) c->op.rilv = op_rows_eff(c);
+    c->op.fail_at = c->op_fail_at;
+}
 
 // scratch layout (offsets in bytes)
 struct Layout {
@@ -237,63 +243,57 @@ Layout layout(const bpgl_ctx* c) {
 
 dim3 grid_tiles(const bpgl_ctx* c) { return dim3((unsigned)((int64_t)c->nseg * c->nchunk)); }
 
-template <typename T, int RPT, bool PIPE>
-int launch_colpass_r(bpgl_ctx* c, int mode, const double* vec, double* slab, int fixed_block) {
-    if (mode == 0 && c->nt_loads)
-        hipLaunchKernelGGL((k_colpass<T, 0, true, RPT, PIPE>), grid_tiles(c), dim3(kThreads), 0, c->stream, c->p, vec,
-                           slab, fixed_block);
-    else if (mode == 0)
-        hipLaunchKernelGGL((k_colpass<T, 0, false, RPT, PIPE>), grid_tiles(c), dim3(kThreads), 0, c->stream, c->p, vec,
-                           slab, fixed_block);
-    else
-        hipLaunchKernelGGL((k_colpass<T, 1, false, 2, false>), grid_tiles(c), dim3(kThreads), 0, c->stream, c->p, vec,
-                           slab, fixed_block);
+// f(Tag<T>{}) for the storage type T of a run-time BPGL_F32 / F64 / BF16
+template <typename T> struct Tag { using type = T; };
+template <typename F>
+auto dispatch_dtype(int dtype, F&& f) {
+    return dispatch<BPGL_F32, BPGL_F64, BPGL_BF16>(dtype, [&](auto d) {
+        constexpr int D = decltype(d)::value;
+        return f(Tag<std::conditional_t<D == BPGL_F32, float, std::conditional_t<D == BPGL_F64, double, bf16_t>>>{});
+    });
+}
+
+using PassFn = void (*)(Params, const double*, double*, int);
+// mode 0: A_b^T vec with the row schedule of col_mode: 0 = 2 rows per trip, 1 = 4 rows per trip, 2 = 2 rows
+// per trip software-pipelined; mode 1: the column norms, one form whatever col_mode and nt_loads say
+int colpass(bpgl_ctx* c, int mode, const double* vec, double* slab, int fixed_block) {
+    const PassFn fn = dispatch_dtype(c->dtype, [&](auto t) -> PassFn {
+        using T = typename decltype(t)::type;
+        if (mode != 0) return &k_colpass<T, 1, false, 2, false>;
+        return dispatch<1, 2, 0>(c->col_mode, [&](auto cm) -> PassFn {
+            constexpr int RPT = decltype(cm)::value == 1 ? 4 : 2;
+            constexpr bool PIPE = decltype(cm)::value == 2;
+            return c->nt_loads ? &k_colpass<T, 0, true, RPT, PIPE> : &k_colpass<T, 0, false, RPT, PIPE>;
+        });
+    });
+    hipLaunchKernelGGL(fn, grid_tiles(c), dim3(kThreads), 0, c->stream, c->p, vec, slab, fixed_block);
     LAUNCH_CHECK("k_colpass");
     return 0;
 }
-// col_mode: 0 = 2 rows per trip, 1 = 4 rows per trip, 2 = 2 rows per trip software-pipelined
-template <typename T>
-int launch_colpass(bpgl_ctx* c, int mode, const double* vec, double* slab, int fixed_block) {
-    switch (c->col_mode) {
-        case 1: return launch_colpass_r<T, 4, false>(c, mode, vec, slab, fixed_block);
-        case 2: return launch_colpass_r<T, 2, true>(c, mode, vec, slab, fixed_block);
-        default: return launch_colpass_r<T, 2, false>(c, mode, vec, slab, fixed_block);
-    }
-}
-int colpass(bpgl_ctx* c, int mode, const double* vec, double* slab, int fixed_block) {
-    switch (c->dtype) {
-        case BPGL_F32: return launch_colpass<float>(c, mode, vec, slab, fixed_block);
-        case BPGL_F64: return launch_colpass<double>(c, mode, vec, slab, fixed_block);
-        default: return launch_colpass<bf16_t>(c, mode, vec, slab, fixed_block);
-    }
-}
-template <typename T>
-int launch_rowpass(bpgl_ctx* c, const double* d, double* slab, int fixed_block) {
-    if (c->nt_loads)
-        hipLaunchKernelGGL((k_rowpass<T, true>), grid_tiles(c), dim3(kThreads), 0, c->stream, c->p, d, slab, fixed_block);
-    else
-        hipLaunchKernelGGL((k_rowpass<T, false>), grid_tiles(c), dim3(kThreads), 0, c->stream, c->p, d, slab, fixed_block);
+int rowpass(bpgl_ctx* c, const double* d, double* slab, int fixed_block) {
+    const PassFn fn = dispatch_dtype(c->dtype, [&](auto t) -> PassFn {
+        using T = typename decltype(t)::type;
+        return c->nt_loads ? &k_rowpass<T, true> : &k_rowpass<T, false>;
+    });
+    hipLaunchKernelGGL(fn, grid_tiles(c), dim3(kThreads), 0, c->stream, c->p, d, slab, fixed_block);
     LAUNCH_CHECK("k_rowpass");
     return 0;
-}
-int rowpass(bpgl_ctx* c, const double* d, double* slab, int fixed_block) {
-    switch (c->dtype) {
-        case BPGL_F32: return launch_rowpass<float>(c, d, slab, fixed_block);
-        case BPGL_F64: return launch_rowpass<double>(c, d, slab, fixed_block);
-        default: return launch_rowpass<bf16_t>(c, d, slab, fixed_block);
-    }
 }
 
 unsigned rowreduce_blocks(const bpgl_ctx* c) {
     return (unsigned)std::min<int64_t>(cdiv(c->m, kRowsPerReduce), kMaxReduceBlocks);
 }
-int rowreduce_p(bpgl_ctx* c, const Params& q, const double* slab, double* out, int mode) {
-    const dim3 g(rowreduce_blocks(c)), b(kThreads);
-    // one batch of loads per wave covers the segments: 4 waves x BATCH >= nseg
-    if (q.nseg <= 4) hipLaunchKernelGGL(k_rowreduce<1>, g, b, 0, c->stream, q, slab, out, mode);
-    else if (q.nseg <= 16) hipLaunchKernelGGL(k_rowreduce<4>, g, b, 0, c->stream, q, slab, out, mode);
-    else hipLaunchKernelGGL(k_rowreduce<16>, g, b, 0, c->stream, q, slab, out, mode);
+// k_rowreduce alone: one batch of loads per wave covers the segments, 4 waves x BATCH >= nseg
+int launch_rowreduce(bpgl_ctx* c, const Params& q, const double* slab, double* out, int mode) {
+    const auto fn = dispatch<1, 4, 16>(q.nseg <= 4 ? 1 : q.nseg <= 16 ? 4 : 16,
+                                       [](auto batch) { return &k_rowreduce<decltype(batch)::value>; });
+    hipLaunchKernelGGL(fn, dim3(rowreduce_blocks(c)), dim3(kThreads), 0, c->stream, q, slab, out, mode);
     LAUNCH_CHECK("k_rowreduce");
+    return 0;
+}
+// ... and, for mode 1, the line search on its partials
+int rowreduce_p(bpgl_ctx* c, const Params& q, const double* slab, double* out, int mode) {
+    if (int rc = launch_rowreduce(c, q, slab, out, mode)) return rc;
     if (mode == 1) {
         hipLaunchKernelGGL(k_linesearch, dim3(1), dim3(kThreads), 0, c->stream, q, (int)rowreduce_blocks(c),
                            (const float*)nullptr);
@@ -329,38 +329,24 @@ Params op_params(const bpgl_ctx* c) {
     q.nparts = c->op_tail_grid;   // shrink partials come from k_onepass_tail
     return q;
 }
-// GPL: granules per lane of the row hand-off (SB <= 64: 1, SB <= 128: 2); RILV: interleaved row groups
-// (instantiated for GPL 1 only: "onepass_rows" applies when SB <= 64)
-template <typename T, int GPL, bool RILV>
-const void* onepass_fn_g() { return (const void*)k_onepass<T, OpRing<T>::NB, OpRing<T>::PF, OpLU<T>::LU, GPL, RILV>; }
-template <typename T>
-const void* onepass_fn_t(int gpl, int rilv) {
-    return gpl == 2 ? onepass_fn_g<T, 2, false>() : gpl == 0 ? onepass_fn_g<T, 0, false>()
-                     : rilv ? onepass_fn_g<T, 1, true>() : onepass_fn_g<T, 1, false>();
-}
-const void* onepass_fn(int dtype, int gpl, int rilv) {
-    return dtype == BPGL_F32 ? onepass_fn_t<float>(gpl, rilv) : dtype == BPGL_F64 ? onepass_fn_t<double>(gpl, rilv)
-                                                                                   : onepass_fn_t<bf16_t>(gpl, rilv);
-}
-template <typename T, int GPL, bool RILV>
-void onepass_launch_g(bpgl_ctx* c) {
-    hipLaunchKernelGGL((k_onepass<T, OpRing<T>::NB, OpRing<T>::PF, OpLU<T>::LU, GPL, RILV>),
-                       dim3((unsigned)(c->op_ngroups * c->op_SB)), dim3(kThreads), 0, c->stream, op_params(c), c->op);
-}
-template <typename T>
-void onepass_launch_t(bpgl_ctx* c) {
-    const int gpl = op_gpl_eff(c);
-    if (gpl == 2) onepass_launch_g<T, 2, false>(c);
-    else if (gpl == 0) onepass_launch_g<T, 0, false>(c);
-    else if (c->op.rilv) onepass_launch_g<T, 1, true>(c);
-    else onepass_launch_g<T, 1, false>(c);
+// The k_onepass instantiation of this context: what onepass_ineligible asks the occupancy of is what
+// onepass_launch launches.  GPL: granules per lane of the row hand-off (op_gpl_eff); RILV: interleaved
+// row groups, instantiated for GPL 1 only ("onepass_rows" applies when SB <= 64: op_rows_eff)
+using OnePassFn = void (*)(Params, OnePassArgs);
+OnePassFn onepass_kernel(const bpgl_ctx* c) {
+    return dispatch_dtype(c->dtype, [&](auto t) -> OnePassFn {
+        using T = typename decltype(t)::type;
+        return dispatch<2, 0, 1>(op_gpl_eff(c), [&](auto g) -> OnePassFn {
+            constexpr int GPL = decltype(g)::value;
+            if constexpr (GPL == 1)
+                if (op_rows_eff(c)) return &k_onepass<T, OpRing<T>::NB, OpRing<T>::PF, OpLU<T>::LU, 1, true>;
+            return &k_onepass<T, OpRing<T>::NB, OpRing<T>::PF, OpLU<T>::LU, GPL, false>;
+        });
+    });
 }
 int onepass_launch(bpgl_ctx* c) {
-    switch (c->dtype) {
-        case BPGL_F32: onepass_launch_t<float>(c); break;
-        case BPGL_F64: onepass_launch_t<double>(c); break;
-        default: onepass_launch_t<bf16_t>(c); break;
-    }
+    hipLaunchKernelGGL(onepass_kernel(c), dim3((unsigned)(c->op_ngroups * c->op_SB)), dim3(kThreads), 0, c->stream,
+                       op_params(c), c->op);
     LAUNCH_CHECK("k_onepass");
     return 0;
 }
@@ -396,24 +382,24 @@ int onepass_tail(bpgl_ctx* c) {
     LAUNCH_CHECK("k_onepass_tail");
     return 0;
 }
-int allreduce_sum(bpgl_ctx* c, double* buf, int64_t count) {
-    ncclResult_t nr = ncclAllReduce(buf, buf, (size_t)count, ncclFloat64, ncclSum, c->comm, c->stream);
+int allreduce_sum(bpgl_ctx* c, void* buf, int64_t count, ncclDataType_t type = ncclFloat64) {
+    ncclResult_t nr = ncclAllReduce(buf, buf, (size_t)count, type, ncclSum, c->comm, c->stream);
     if (nr != ncclSuccess) return fail(BPGL_E_RCCL, "ncclAllReduce: %s", ncclGetErrorString(nr));
     return 0;
 }
-// this rank's A^T r into dst (row shards: a partial over ranks)
-int onepass_local_gradient(bpgl_ctx* c, double* dst) {
-    int rc;
-    if ((rc = colpass(c, 0, c->p.r, c->p.slab_g, -1))) return rc;
+// A_b^T vec (mode 1: the column norms of A_b) for block `block` (-1: the solver's) through the split-K
+// slab into dst, and 1 / dst into rdst when given
+int block_mtv(bpgl_ctx* c, int mode, const double* vec, int block, double* dst, double* rdst) {
+    if (int rc = colpass(c, mode, vec, c->p.slab_g, block)) return rc;
     hipLaunchKernelGGL(k_colreduce, dim3((unsigned)cdiv(c->wp, kThreads)), dim3(kThreads), 0, c->stream, c->p.slab_g,
-                       c->wp, c->nchunk, dst, (double*)nullptr);
+                       c->wp, c->nchunk, dst, rdst);
     LAUNCH_CHECK("k_colreduce");
     return 0;
 }
 // exact g = A^T r into G (at reset and every op_refresh iterations); row shards sum it over ranks
 int onepass_refresh(bpgl_ctx* c) {
     int rc;
-    if ((rc = onepass_local_gradient(c, c->op.G))) return rc;
+    if ((rc = block_mtv(c, 0, c->p.r, -1, c->op.G, nullptr))) return rc;   // this rank's A^T r
     if (c->rows && c->comm && (rc = allreduce_sum(c, c->op.G, c->wp))) return rc;
     return onepass_tail<false>(c);   // the shrink of the next iteration from the exact g
 }
@@ -423,7 +409,7 @@ const char* onepass_ineligible(bpgl_ctx* c) {
     if (!c->rows && (c->nranks != 1 || c->comm || c->external))
         return "column shards need a single rank without a communicator (row shards run it on several)";
     int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, onepass_fn(c->dtype, op_gpl_eff(c), op_rows_eff(c)), kThreads, 0) != hipSuccess || nb < 1)
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)onepass_kernel(c), kThreads, 0) != hipSuccess || nb < 1)
         return "kernel does not fit on a CU";
     if ((int64_t)c->op_ngroups * c->op_SB > (int64_t)nb * c->cus) return "grid exceeds the resident capacity";
     return nullptr;
@@ -435,75 +421,32 @@ int check_ready(const bpgl_ctx* c) {
     return 0;
 }
 
-// kinds: 0 colpass, 1 shrink, 2 rowpass, 3 rowreduce, 4 allreduce, 5 step, 6 update, 7 onepass;
-// event 2 * (it * kinds + kind) + {0: start, 1: end}.  Kind 8 (the refresh, not in every
-// iteration) has its own event list, 2 per refresh.
-void ev_record(bpgl_ctx* c, int64_t it, int kind, int end) {
-    if (!c->timing) return;
-    if (kind == 8) {
-        const size_t idx = 2 * (size_t)c->ref_timed + end;
-        while (c->ref_evs.size() <= idx) {
-            hipEvent_t e;
-            if (hipEventCreate(&e) != hipSuccess) return;
-            c->ref_evs.push_back(e);
-        }
-        (void)hipEventRecord(c->ref_evs[idx], c->stream);
-        if (end) c->ref_timed++;
-        c->kind_used[kind] = true;
-        return;
-    }
-    const size_t idx = 2 * ((size_t)it * kTimedKinds + kind) + end;
-    while (c->evs.size() <= idx) {
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) return;
-        c->evs.push_back(e);
-    }
-    (void)hipEventRecord(c->evs[idx], c->stream);
-    c->kind_used[kind] = true;
-}
-
-// phase 0: colpass, shrink, rowpass, rowreduce [, allreduce, step]; phase 1: update.
-// With the caller doing the exchange (external ranks) phase 0 stops after
-// rowreduce and phase 1 starts with the step.
-// one-pass iteration, two kernels: k_onepass (s23 and the U partials; its row groups also
+// Each launch below sits in c->tm.timed(kind, it, ...) with the kinds listed at bpgl_ctx::tm.
+//
+// one-pass iteration, two kernels: phase 0: k_onepass (s23 and the U partials; its row groups also
 // fold r.s23 and s23.s23, and the last group to finish runs the line search); phase 1:
 // k_onepass_tail (x, Ax, r, g += gamma U and the next iteration's shrink)
 //
 // Row shards: k_onepass, k_onepass_fold -> exchange buffer [U | r.s23 | s23.s23 | failed],
 // all-reduce (RCCL); phase 1: k_onepass_tail, which runs the line search on the summed scalars
-// at its head and then applies the summed U.  With the exchange done by the caller (external
+// at its head (o.abe: the fold pre-summed the shrink partials; [r.s23, s23.s23] come from the
+// exchange buffer) and then applies the summed U.  With the exchange done by the caller (external
 // ranks) phase 0 ends after the fold and phase 1 is the tail.
-int enqueue_phase_onepass_rows(bpgl_ctx* c, int64_t it, int phase) {
+int enqueue_phase_onepass(bpgl_ctx* c, int64_t it, int phase) {
     int rc;
-    if (phase == 0) {
-        ev_record(c, it, 7, 0);
-        if ((rc = onepass_launch(c))) return rc;
-        ev_record(c, it, 7, 1);
-        float* xf = xch_f32(c) ? reinterpret_cast<float*>(c->p.comm) : nullptr;
-        ev_record(c, it, 3, 0);
+    if (phase == 1) return c->tm.timed(6, it, [&] { return onepass_tail<true>(c); });
+    if ((rc = c->tm.timed(7, it, [&] { return onepass_launch(c); })) || !c->rows) return rc;
+    float* xf = xch_f32(c) ? reinterpret_cast<float*>(c->p.comm) : nullptr;
+    rc = c->tm.timed(3, it, [&] {
         hipLaunchKernelGGL(k_onepass_fold, dim3((unsigned)std::min<int64_t>(cdiv(c->wp, kThreads), 1024) + 1),
                            dim3(kThreads), 0, c->stream, op_params(c), c->op, c->p.comm, xf);
         LAUNCH_CHECK("k_onepass_fold");
-        ev_record(c, it, 3, 1);
-        if (c->comm) {
-            ev_record(c, it, 4, 0);
-            if (xf) {
-                ncclResult_t nr = ncclAllReduce(xf, xf, (size_t)(c->wp + 5), ncclFloat32, ncclSum, c->comm, c->stream);
-                if (nr != ncclSuccess) return fail(BPGL_E_RCCL, "ncclAllReduce: %s", ncclGetErrorString(nr));
-            } else if ((rc = allreduce_sum(c, c->p.comm, c->wp + 3))) {
-                return rc;
-            }
-            ev_record(c, it, 4, 1);
-        }
-    }
-    // the line search runs at the head of k_onepass_tail (o.abe: the fold pre-summed the shrink
-    // partials; [r.s23, s23.s23] come from the exchange buffer)
-    if (phase == 1) {
-        ev_record(c, it, 6, 0);
-        if ((rc = onepass_tail<true>(c))) return rc;
-        ev_record(c, it, 6, 1);
-    }
-    return 0;
+        return 0;
+    });
+    if (rc || !c->comm) return rc;
+    return c->tm.timed(4, it, [&] {
+        return xf ? allreduce_sum(c, xf, c->wp + 5, ncclFloat32) : allreduce_sum(c, c->p.comm, c->wp + 3);
+    });
 }
 
 // Row shards on the two-pass kernels (RCCL ranks; after a failed one-pass hand-off, or with
@@ -514,92 +457,62 @@ int enqueue_phase_onepass_rows(bpgl_ctx* c, int64_t it, int phase) {
 // but no co-residency requirement.
 int enqueue_phase_rows_twopass(bpgl_ctx* c, int64_t it, int phase) {
     int rc;
-    if (phase == 0) {
-        ev_record(c, it, 0, 0);
-        if ((rc = onepass_refresh(c))) return rc;     // exact g, then the shrink (tail<false>)
-        ev_record(c, it, 0, 1);
-        ev_record(c, it, 2, 0);
-        if ((rc = rowpass(c, c->p.D, c->p.slab_s, -1))) return rc;
-        const dim3 g(rowreduce_blocks(c)), b(kThreads);
-        if (c->p.nseg <= 4) hipLaunchKernelGGL(k_rowreduce<1>, g, b, 0, c->stream, c->p, c->p.slab_s, c->op.S, 1);
-        else if (c->p.nseg <= 16) hipLaunchKernelGGL(k_rowreduce<4>, g, b, 0, c->stream, c->p, c->p.slab_s, c->op.S, 1);
-        else hipLaunchKernelGGL(k_rowreduce<16>, g, b, 0, c->stream, c->p, c->p.slab_s, c->op.S, 1);
-        LAUNCH_CHECK("k_rowreduce");
-        ev_record(c, it, 2, 1);
-        ev_record(c, it, 3, 0);
+    if (phase == 1) return c->tm.timed(6, it, [&] { return onepass_tail<true>(c); });
+    // exact g, then the shrink (tail<false>)
+    if ((rc = c->tm.timed(0, it, [&] { return onepass_refresh(c); }))) return rc;
+    rc = c->tm.timed(2, it, [&] {   // k_rowreduce alone: the line search follows the all-reduce
+        const int e = rowpass(c, c->p.D, c->p.slab_s, -1);
+        return e ? e : launch_rowreduce(c, c->p, c->p.slab_s, c->op.S, 1);
+    });
+    if (rc) return rc;
+    rc = c->tm.timed(3, it, [&] {
         HIP_TRY(hipMemsetAsync(c->p.comm, 0, 8 * c->wp, c->stream));
         hipLaunchKernelGGL(k_rows2_fold, dim3(1), dim3(kThreads), 0, c->stream, op_params(c), c->op, c->p.comm,
                            (int)rowreduce_blocks(c));
         LAUNCH_CHECK("k_rows2_fold");
-        ev_record(c, it, 3, 1);
-        ev_record(c, it, 4, 0);
-        if (c->comm && (rc = allreduce_sum(c, c->p.comm + c->wp, 3))) return rc;
-        ev_record(c, it, 4, 1);
-    } else {
-        ev_record(c, it, 6, 0);
-        if ((rc = onepass_tail<true>(c))) return rc;
-        ev_record(c, it, 6, 1);
-    }
-    return 0;
+        return 0;
+    });
+    if (rc) return rc;
+    return c->tm.timed(4, it, [&] { return c->comm ? allreduce_sum(c, c->p.comm + c->wp, 3) : 0; });
 }
 
-int enqueue_phase_onepass(bpgl_ctx* c, int64_t it, int phase) {
-    int rc;
-    if (c->rows) return enqueue_phase_onepass_rows(c, it, phase);
-    if (phase == 0) {   // k_onepass ends with the line search (its last row group)
-        ev_record(c, it, 7, 0);
-        if ((rc = onepass_launch(c))) return rc;
-        ev_record(c, it, 7, 1);
-    } else {
-        ev_record(c, it, 6, 0);
-        if ((rc = onepass_tail<true>(c))) return rc;
-        ev_record(c, it, 6, 1);
-    }
-    return 0;
-}
-
+// phase 0: colpass, shrink, rowpass, rowreduce [, allreduce, step]; phase 1: update.
+// With the caller doing the exchange (external ranks) phase 0 stops after
+// rowreduce and phase 1 starts with the step.
 int enqueue_phase(bpgl_ctx* c, int64_t it, int phase) {
     int rc;
     if (c->op_on) return enqueue_phase_onepass(c, it, phase);
     if (c->rows) return enqueue_phase_rows_twopass(c, it, phase);
     const bool multi = c->comm != nullptr || c->external;
     if (phase == 0) {
-        ev_record(c, it, 0, 0);
-        if ((rc = colpass(c, 0, c->p.r, c->p.slab_g, -1))) return rc;
-        ev_record(c, it, 0, 1);
-        ev_record(c, it, 1, 0);
-        hipLaunchKernelGGL(k_shrink, dim3((unsigned)c->nparts), dim3(kThreads), 0, c->stream, c->p);
-        LAUNCH_CHECK("k_shrink");
-        ev_record(c, it, 1, 1);
-        ev_record(c, it, 2, 0);
-        if ((rc = rowpass(c, c->p.D, c->p.slab_s, -1))) return rc;
-        ev_record(c, it, 2, 1);
-        ev_record(c, it, 3, 0);
-        if ((rc = rowreduce(c, c->p.slab_s, c->p.comm, multi ? 2 : 1))) return rc;
-        ev_record(c, it, 3, 1);
-        if (c->comm) {
-            ev_record(c, it, 4, 0);
-            ncclResult_t nr = ncclAllReduce(c->p.comm, c->p.comm, (size_t)(c->m + 2 + c->nranks), ncclFloat64,
-                                            ncclSum, c->comm, c->stream);
-            if (nr != ncclSuccess) return fail(BPGL_E_RCCL, "ncclAllReduce: %s", ncclGetErrorString(nr));
-            ev_record(c, it, 4, 1);
-        }
+        if ((rc = c->tm.timed(0, it, [&] { return colpass(c, 0, c->p.r, c->p.slab_g, -1); }))) return rc;
+        rc = c->tm.timed(1, it, [&] {
+            hipLaunchKernelGGL(k_shrink, dim3((unsigned)c->nparts), dim3(kThreads), 0, c->stream, c->p);
+            LAUNCH_CHECK("k_shrink");
+            return 0;
+        });
+        if (rc) return rc;
+        if ((rc = c->tm.timed(2, it, [&] { return rowpass(c, c->p.D, c->p.slab_s, -1); }))) return rc;
+        if ((rc = c->tm.timed(3, it, [&] { return rowreduce(c, c->p.slab_s, c->p.comm, multi ? 2 : 1); }))) return rc;
+        if (c->comm && (rc = c->tm.timed(4, it, [&] { return allreduce_sum(c, c->p.comm, c->m + 2 + c->nranks); })))
+            return rc;
     }
     if ((phase == 0 && c->comm) || (phase == 1 && c->external)) {
-        ev_record(c, it, 5, 0);
-        hipLaunchKernelGGL(k_step, dim3(1), dim3(kStepThreads), 0, c->stream, c->p);
-        LAUNCH_CHECK("k_step");
-        ev_record(c, it, 5, 1);
+        rc = c->tm.timed(5, it, [&] {
+            hipLaunchKernelGGL(k_step, dim3(1), dim3(kStepThreads), 0, c->stream, c->p);
+            LAUNCH_CHECK("k_step");
+            return 0;
+        });
+        if (rc) return rc;
     }
-    if (phase == 1) {
-        ev_record(c, it, 6, 0);
+    if (phase != 1) return 0;
+    return c->tm.timed(6, it, [&] {
         const int64_t nupd = std::max<int64_t>(c->wp, c->m);
         const unsigned ublocks = (unsigned)std::min<int64_t>(cdiv(nupd, kThreads), 1024);
         hipLaunchKernelGGL(k_update, dim3(ublocks), dim3(kThreads), 0, c->stream, c->p);
         LAUNCH_CHECK("k_update");
-        ev_record(c, it, 6, 1);
-    }
-    return 0;
+        return 0;
+    });
 }
 
 // One block update, enqueued on c->stream.  The block index and every
@@ -615,30 +528,20 @@ int enqueue_iteration(bpgl_ctx* c, int64_t it) {
 // an all-reduce node), the others graph_max
 int graph_cap(const bpgl_ctx* c) { return c->comm ? std::min(c->graph_max, kGraphIters) : c->graph_max; }
 
-// hipGraphs of 1, 2, 4, ... graph_cap iterations (c->use_graph), uploaded to the device here so
-// the first replay inside a caller's timed region pays no upload
+// hipGraphs of 1, 2, 4, ... graph_cap iterations (c->use_graph), captured with timing off
 int capture_graphs(bpgl_ctx* c) {
     drop_graphs(c);
     if (!c->use_graph) return 0;
     int rc = 0;
-    const bool was_timing = c->timing;
-    c->timing = false;
-    for (int level = 0; level < kGraphLevels && (1 << level) <= graph_cap(c) && !rc; ++level) {
-        const int iters = 1 << level;
-        hipGraph_t graph = nullptr;
-        HIP_TRY(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-        for (int k = 0; k < iters && !rc; ++k) rc = enqueue_iteration(c, 0);
-        hipError_t ec = hipStreamEndCapture(c->stream, &graph);
-        if (rc) { if (graph) (void)hipGraphDestroy(graph); break; }
-        if (ec != hipSuccess) { rc = fail(BPGL_E_HIP, "hipStreamEndCapture: %s", hipGetErrorString(ec)); break; }
-        hipGraphExec_t* dst = &c->gexec[level];
-        hipError_t ei = hipGraphInstantiate(dst, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (ei != hipSuccess) { rc = fail(BPGL_E_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ei)); break; }
-        if ((ei = hipGraphUpload(*dst, c->stream)) != hipSuccess)
-            rc = fail(BPGL_E_HIP, "hipGraphUpload: %s", hipGetErrorString(ei));
-    }
-    c->timing = was_timing;
+    const bool was_timing = c->tm.on;
+    c->tm.on = false;
+    for (int level = 0; level < kGraphLevels && (1 << level) <= graph_cap(c) && !rc; ++level)
+        rc = capture_graph(c->stream, &c->gexec[level], [&] {
+            int e = 0;
+            for (int k = 0; k < (1 << level) && !e; ++k) e = enqueue_iteration(c, 0);
+            return e;
+        });
+    c->tm.on = was_timing;
     return rc;
 }
 
@@ -649,23 +552,22 @@ int step_impl(bpgl_ctx* c, int64_t n_iter) {
     const int64_t K = c->op_on ? c->op_refresh : 0;
     for (int64_t i = 0; i < n_iter;) {
         if (K > 0 && c->op_t > 0 && c->op_t % K == 0) {
-            ev_record(c, c->timed_iters, 8, 0);
             c->n_refresh++;
-            if ((rc = onepass_refresh(c))) return rc;
-            ev_record(c, c->timed_iters, 8, 1);
+            if ((rc = c->ref_tm.timed(0, c->ref_tm.iters, [&] { return onepass_refresh(c); }))) return rc;
+            if (c->ref_tm.on) c->ref_tm.iters++;
         }
         const int64_t room = K > 0 ? std::min<int64_t>(n_iter - i, K - c->op_t % K) : n_iter - i;
         int64_t k = 1;
         int level = -1;   // the largest captured graph that fits the room
-        if (!c->timing)
+        if (!c->tm.on)
             for (int j = kGraphLevels - 1; j >= 0 && level < 0; --j)
                 if (c->gexec[j] && room >= (int64_t(1) << j)) level = j;
         if (level >= 0) {
             HIP_TRY(hipGraphLaunch(c->gexec[level], c->stream));
             k = int64_t(1) << level;
         } else {
-            if ((rc = enqueue_iteration(c, c->timing ? c->timed_iters : 0))) return rc;
-            if (c->timing) c->timed_iters++;
+            if ((rc = enqueue_iteration(c, c->tm.on ? c->tm.iters : 0))) return rc;
+            if (c->tm.on) c->tm.iters++;
         }
         i += k;
         c->op_t += k;
@@ -692,7 +594,7 @@ int recover_onepass(bpgl_ctx* c, DevState& st) {
         HIP_TRY(hipMemsetAsync(&c->p.st->op_fail, 0, sizeof st.op_fail, c->stream));
         const int64_t t = st.t;
         c->op_fail_at = -1;   // the test hook fires once
-        c->op.fail_at = -1;
+        knob_mirrors(c);
         if (c->external)
             return fail(BPGL_E_EXCHANGE, "one-pass row hand-off timed out (blocks not co-resident); iterations from "
                                          "t = %lld on were not applied and the solver state is intact: run them again",
@@ -708,6 +610,55 @@ int recover_onepass(bpgl_ctx* c, DevState& st) {
     }
     return 0;
 }
+
+int check_rank(int rank, int nranks) {
+    if (nranks < 1 || nranks > kMaxRanks || rank < 0 || rank >= nranks)
+        return fail(BPGL_E_ARG, "bad rank %d / nranks %d", rank, nranks);
+    return 0;
+}
+// this context's place among the ranks (check_rank passed); an earlier communicator goes
+void set_rank(bpgl_ctx* c, int rank, int nranks) {
+    if (c->comm) { ncclCommDestroy(c->comm); c->comm = nullptr; }
+    c->rank = c->p.rank = rank;
+    c->nranks = c->p.nranks = nranks;
+}
+
+// bpgl_set_tuning's keys with a plain rule: the admissible values [lo, hi] (and how an error message
+// names them), where the value goes, and what a change costs.  "cus" and "onepass_fail_at" have lines
+// of their own there.
+enum : unsigned {
+    kDropGraphs = 1,   // the captured graphs bake the old value in
+    kNeedsReset = 2,   // ... and so does the solver state: bpgl_solver_step fails until a bpgl_solver_reset
+    kAnyNonZero = 4,   // any non-zero value means 1
+    kPowerOfTwo = 8,
+    kClamp30 = 16,     // values above 2^30 are stored as 2^30
+};
+struct Knob {
+    const char* key;
+    int64_t lo, hi;
+    const char* admissible;
+    int bpgl_ctx::*member;
+    unsigned flags;
+};
+static_assert(kGraphMaxIters == 64, "the graph_max message below names it");
+const Knob kKnobs[] = {
+    {"reverse_rows", 0, 1, "0 or 1", &bpgl_ctx::reverse_rows, kAnyNonZero | kDropGraphs | kNeedsReset},
+    {"nt_loads", 0, 1, "0 or 1", &bpgl_ctx::nt_loads, kAnyNonZero | kDropGraphs | kNeedsReset},
+    {"tail_permille", 0, 1000, "in [0, 1000]", &bpgl_ctx::tail_permille, kDropGraphs | kNeedsReset},
+    {"col_mode", 0, 2, "0, 1 or 2", &bpgl_ctx::col_mode, kDropGraphs | kNeedsReset},
+    {"onepass", -1, 1, "-1, 0 or 1", &bpgl_ctx::onepass, kDropGraphs | kNeedsReset},
+    {"onepass_cache_permille", -1, 1000, "-1 (auto) or in [0, 1000]", &bpgl_ctx::op_cache, kDropGraphs | kNeedsReset},
+    {"onepass_rows", -1, 1, "-1 (auto), 0 or 1", &bpgl_ctx::op_rows, kDropGraphs | kNeedsReset},
+    {"onepass_sb1", -1, 0, "-1 (auto) or 0", &bpgl_ctx::op_sb1, kDropGraphs | kNeedsReset},
+    {"exchange_fp32", -1, 1, "-1, 0 or 1", &bpgl_ctx::xch32, kDropGraphs | kNeedsReset},
+    // speed only: the largest hipGraph of iterations (replays per run)
+    {"graph_max", 1, kGraphMaxIters, "a power of two in [1, 64]", &bpgl_ctx::graph_max,
+     kPowerOfTwo | kDropGraphs | kNeedsReset},
+    // speed only: where the tail's residual update runs (bitwise neutral)
+    {"tail_row_blocks", 0, 1, "0 or 1", &bpgl_ctx::op_rowb, kDropGraphs},
+    // read by every bpgl_solver_step: nothing to drop
+    {"onepass_refresh", 0, INT64_MAX, ">= 0", &bpgl_ctx::op_refresh, kClamp30},
+};
 
 }  // namespace
 
@@ -770,6 +721,7 @@ int bpgl_create(bpgl_ctx** out, int device, int a_dtype, int64_t m, int64_t n_lo
         }
         c->own_stream = true;
     }
+    c->tm.stream = c->ref_tm.stream = c->stream;
     {   // a CU-masked stream (bpgl_stream_create): the persistent one-pass grid is sized to the CUs
         // the stream may use, so all of its blocks stay resident beside other masked streams
         const int n = stream_cus(c->stream, c->dev_cus);
@@ -794,8 +746,8 @@ void bpgl_destroy(bpgl_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);   // destroy path: nothing to report to
     drop_graphs(c);
-    for (auto e : c->evs) (void)hipEventDestroy(e);
-    for (auto e : c->ref_evs) (void)hipEventDestroy(e);
+    for (auto e : c->tm.evs) (void)hipEventDestroy(e);
+    for (auto e : c->ref_tm.evs) (void)hipEventDestroy(e);
     if (c->comm) ncclCommDestroy(c->comm);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -854,8 +806,6 @@ int bpgl_bind(bpgl_ctx* c, const void* A, int64_t lda, int64_t block_stride, voi
     p.D = (double*)(s + L.D);
     p.parts = (double*)(s + L.parts);
     p.parts2 = (double*)(s + L.parts2);
-    p.reverse_rows = c->reverse_rows;
-    p.tail_permille = c->tail_permille;
     p.comm = (double*)(s + L.comm);
     p.r = (double*)(s + L.r);
     p.Ax = (double*)(s + L.Ax);
@@ -879,10 +829,8 @@ int bpgl_bind(bpgl_ctx* c, const void* A, int64_t lda, int64_t block_stride, voi
         c->op.xl = c->op_xl;
         c->op.ls = c->rows ? 0 : 1;   // row shards: the line search follows the all-reduce (in the tail)
         c->op.abe = c->rows ? (double*)(s + L.opABE) : nullptr;
-        c->op.cache_permille = op_cache_eff(c);
-        c->op.rilv = op_rows_eff(c);
     }
-    c->op.fail_at = c->op_fail_at;
+    knob_mirrors(c);
     HIP_TRY(hipSetDevice(c->device));
     if (c->op_shape) {
         HIP_TRY(hipMemsetAsync(s + L.opPG, 0, 8 * c->m * c->op_SB, c->stream));   // tag 0: never written
@@ -903,12 +851,9 @@ int bpgl_diag_ata(bpgl_ctx* c, double* out) {
     if ((rc = check_ready(c))) return rc;
     HIP_TRY(hipSetDevice(c->device));
     for (int b = 0; b < c->nblock; ++b) {
-        if ((rc = colpass(c, 1, nullptr, c->p.slab_g, b))) return rc;
         double* dst = const_cast<double*>(c->p.diag) + (int64_t)b * c->wp;
         double* rdst = const_cast<double*>(c->p.rec) + (int64_t)b * c->wp;
-        hipLaunchKernelGGL(k_colreduce, dim3((unsigned)cdiv(c->wp, kThreads)), dim3(kThreads), 0, c->stream,
-                           c->p.slab_g, c->wp, c->nchunk, dst, rdst);
-        LAUNCH_CHECK("k_colreduce");
+        if ((rc = block_mtv(c, 1, nullptr, b, dst, rdst))) return rc;
     }
     if (c->rows && c->comm) {   // row shards: column norms are sums over ranks
         double* dg = const_cast<double*>(c->p.diag);
@@ -956,11 +901,7 @@ int bpgl_mtv(bpgl_ctx* c, int32_t block, const double* r, double* g) {
     if (block < 0 || block >= c->nblock) return fail(BPGL_E_ARG, "block %d out of range", block);
     if (!r || !g) return fail(BPGL_E_ARG, "null vector");
     HIP_TRY(hipSetDevice(c->device));
-    if ((rc = colpass(c, 0, r, c->p.slab_g, block))) return rc;
-    hipLaunchKernelGGL(k_colreduce, dim3((unsigned)cdiv(c->wp, kThreads)), dim3(kThreads), 0, c->stream,
-                       c->p.slab_g, c->wp, c->nchunk, g, (double*)nullptr);
-    LAUNCH_CHECK("k_colreduce");
-    return 0;
+    return block_mtv(c, 0, r, block, g, nullptr);
 }
 
 int bpgl_mv(bpgl_ctx* c, int32_t block, const double* d, double* s) {
@@ -984,15 +925,11 @@ int bpgl_comm_unique_id(void* out128) {
 }
 
 int bpgl_comm_init(bpgl_ctx* c, const void* uid, int rank, int nranks) {
+    int rc;
     if (!c || !uid) return fail(BPGL_E_ARG, "null argument");
-    if (nranks < 1 || nranks > kMaxRanks || rank < 0 || rank >= nranks)
-        return fail(BPGL_E_ARG, "bad rank %d / nranks %d", rank, nranks);
+    if ((rc = check_rank(rank, nranks))) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    if (c->comm) { ncclCommDestroy(c->comm); c->comm = nullptr; }
-    c->rank = rank;
-    c->nranks = nranks;
-    c->p.rank = rank;
-    c->p.nranks = nranks;
+    set_rank(c, rank, nranks);
     {   // also for nranks == 1: an explicit request (it runs the sharded code path on one GPU)
         ncclUniqueId id;
         memcpy(&id, uid, 128);
@@ -1006,14 +943,10 @@ int bpgl_comm_init(bpgl_ctx* c, const void* uid, int rank, int nranks) {
 }
 
 int bpgl_set_ranks(bpgl_ctx* c, int rank, int nranks) {
+    int rc;
     if (!c) return fail(BPGL_E_ARG, "null context");
-    if (nranks < 1 || nranks > kMaxRanks || rank < 0 || rank >= nranks)
-        return fail(BPGL_E_ARG, "bad rank %d / nranks %d", rank, nranks);
-    if (c->comm) { ncclCommDestroy(c->comm); c->comm = nullptr; }
-    c->rank = rank;
-    c->nranks = nranks;
-    c->p.rank = rank;
-    c->p.nranks = nranks;
+    if ((rc = check_rank(rank, nranks))) return rc;
+    set_rank(c, rank, nranks);
     c->p.has_comm = 0;
     c->external = nranks > 1;
     drop_graphs(c);
@@ -1031,7 +964,7 @@ int bpgl_solver_phase(bpgl_ctx* c, int phase) {
         if (!(c->rows && c->external && c->op_on))
             return fail(BPGL_E_STATE, "phases 2 and 3 exist for external row shards only");
         if (phase == 2) {
-            if ((rc = onepass_local_gradient(c, c->p.comm))) return rc;
+            if ((rc = block_mtv(c, 0, c->p.r, -1, c->p.comm, nullptr))) return rc;   // this rank's partial of A^T r
             HIP_TRY(hipMemsetAsync(c->p.comm + c->wp, 0, 24, c->stream));
             c->op_refresh_pending = true;
             return 0;
@@ -1075,12 +1008,8 @@ int bpgl_solver_reset(bpgl_ctx* c, const double* b, double mu, double* x, const 
         if ((rc = rowpass(c, x + (int64_t)k * c->wp, p.slab_s, k))) return rc;
         if ((rc = rowreduce(c, p.slab_s, p.Ax + (int64_t)k * c->m, 0))) return rc;
     }
-    if (c->comm && !c->rows) {
-        // column-sharded ranks: every Ax_k is a sum over ranks (row shards: Ax rows are local)
-        ncclResult_t nr = ncclAllReduce(p.Ax, p.Ax, (size_t)c->nblock * c->m, ncclFloat64, ncclSum, c->comm,
-                                        c->stream);
-        if (nr != ncclSuccess) return fail(BPGL_E_RCCL, "ncclAllReduce: %s", ncclGetErrorString(nr));
-    }
+    // column-sharded ranks: every Ax_k is a sum over ranks (row shards: Ax rows are local)
+    if (c->comm && !c->rows && (rc = allreduce_sum(c, p.Ax, (int64_t)c->nblock * c->m))) return rc;
     hipLaunchKernelGGL(k_reset, dim3((unsigned)std::min<int64_t>(cdiv(c->m, kThreads), 1024)), dim3(kThreads), 0,
                        c->stream, p);
     LAUNCH_CHECK("k_reset");
@@ -1102,7 +1031,7 @@ int bpgl_solver_reset(bpgl_ctx* c, const double* b, double mu, double* x, const 
     c->req_t = 0;
     c->n_refresh = c->n_fallback = 0;
     c->solver = true;
-    c->timed_iters = 0;
+    c->tm.iters = 0;
     return 0;
 }
 
@@ -1170,12 +1099,8 @@ int bpgl_solver_gap(bpgl_ctx* c, double* g_all, uint8_t* keep, double* out6) {
     // exact g = A_b^T r for every block, through the split-K slab (free between iterations) into the
     // caller's buffer: the carried gradient op.G and every other piece of solver state stay untouched
     const int64_t n = (int64_t)c->nblock * c->wp;
-    for (int b = 0; b < c->nblock; ++b) {
-        if ((rc = colpass(c, 0, c->p.r, c->p.slab_g, b))) return rc;
-        hipLaunchKernelGGL(k_colreduce, dim3((unsigned)cdiv(c->wp, kThreads)), dim3(kThreads), 0, c->stream,
-                           c->p.slab_g, c->wp, c->nchunk, g_all + (int64_t)b * c->wp, (double*)nullptr);
-        LAUNCH_CHECK("k_colreduce");
-    }
+    for (int b = 0; b < c->nblock; ++b)
+        if ((rc = block_mtv(c, 0, c->p.r, b, g_all + (int64_t)b * c->wp, nullptr))) return rc;
     const int nparts = (int)std::min<int64_t>(cdiv(std::max<int64_t>(c->m, n), kThreads), kGapBlocks);
     double* res = c->gap_buf + 4 * kGapBlocks;
     hipLaunchKernelGGL(k_gap_partials, dim3((unsigned)nparts), dim3(kThreads), 0, c->stream, c->p, g_all, c->gap_buf);
@@ -1199,27 +1124,8 @@ int bpgl_solver_gap(bpgl_ctx* c, double* g_all, uint8_t* keep, double* out6) {
 int bpgl_gather_columns(bpgl_ctx* c, const int32_t* cols, int64_t n_out, void* A_out, int64_t lda_out) {
     int rc;
     if ((rc = check_ready(c))) return rc;
-    if (!cols || !A_out) return fail(BPGL_E_ARG, "cols and A_out must be non-null");
-    const int V = vec_elems(c->dtype);
-    if (n_out <= 0) return fail(BPGL_E_ARG, "n_out must be > 0");
-    if (lda_out < n_out || lda_out % V)
-        return fail(BPGL_E_ARG, "lda_out (%lld) must be >= n_out (%lld) and a multiple of %d", (long long)lda_out,
-                    (long long)n_out, V);
-    if (((uintptr_t)A_out) % 16) return fail(BPGL_E_ARG, "A_out must be 16-byte aligned");
-    if (lda_out / V > (int64_t)0x7fffffff * kThreads) return fail(BPGL_E_ARG, "lda_out too large");
-    HIP_TRY(hipSetDevice(c->device));
-    GatherArgs a{c->A, c->lda, c->block_stride, c->w, (int64_t)c->nblock * c->w, c->m, cols, n_out, A_out, lda_out};
-    const int64_t gx = cdiv(lda_out / V, kThreads);
-    // about 4096 blocks; each thread walks rows blockIdx.y, + gridDim.y, ... with its column offsets in registers
-    const int64_t gy = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(c->m, 65535), cdiv(4096, gx)));
-    const dim3 g((unsigned)gx, (unsigned)gy), b(kThreads);
-    switch (c->dtype) {
-        case BPGL_F32: hipLaunchKernelGGL(k_gather_cols<4>, g, b, 0, c->stream, a); break;
-        case BPGL_F64: hipLaunchKernelGGL(k_gather_cols<8>, g, b, 0, c->stream, a); break;
-        default: hipLaunchKernelGGL(k_gather_cols<2>, g, b, 0, c->stream, a); break;
-    }
-    LAUNCH_CHECK("k_gather_cols");
-    return 0;
+    const GatherArgs a{c->A, c->lda, c->block_stride, c->w, (int64_t)c->nblock * c->w, c->m, cols, n_out, A_out, lda_out};
+    return gather_columns<4, 8, 2>(c->device, c->stream, 16 / vec_elems(c->dtype), a);
 }
 
 int bpgl_iterate(bpgl_ctx* c, int64_t n_iter, const int32_t* order, double mu, const double* b, double* x,
@@ -1238,79 +1144,7 @@ int bpgl_iterate(bpgl_ctx* c, int64_t n_iter, const int32_t* order, double mu, c
 
 int bpgl_set_tuning(bpgl_ctx* c, const char* key, int64_t value) {
     if (!c || !key) return fail(BPGL_E_ARG, "null argument");
-    if (!strcmp(key, "reverse_rows")) {
-        c->reverse_rows = value != 0;
-        c->p.reverse_rows = c->reverse_rows;
-        drop_graphs(c);
-        c->solver = false;   // a new bpgl_solver_reset re-captures the iteration
-        return 0;
-    }
-    if (!strcmp(key, "tail_permille")) {
-        if (value < 0 || value > 1000) return fail(BPGL_E_ARG, "tail_permille must be in [0, 1000]");
-        c->tail_permille = (int)value;
-        c->p.tail_permille = c->tail_permille;
-        drop_graphs(c);
-        c->solver = false;
-        return 0;
-    }
-    if (!strcmp(key, "col_mode")) {
-        if (value < 0 || value > 2) return fail(BPGL_E_ARG, "col_mode must be 0, 1 or 2");
-        c->col_mode = (int)value;
-        drop_graphs(c);
-        c->solver = false;
-        return 0;
-    }
-    if (!strcmp(key, "onepass")) {
-        if (value < -1 || value > 1) return fail(BPGL_E_ARG, "onepass must be -1, 0 or 1");
-        c->onepass = (int)value;
-        drop_graphs(c);
-        c->solver = false;
-        return 0;
-    }
-    if (!strcmp(key, "tail_row_blocks")) {   // speed only: where the tail's residual update runs (bitwise neutral)
-        if (value != 0 && value != 1) return fail(BPGL_E_ARG, "tail_row_blocks must be 0 or 1");
-        c->op_rowb = (int)value;
-        drop_graphs(c);
-        return 0;
-    }
-    if (!strcmp(key, "onepass_cache_permille")) {
-        if (value < -1 || value > 1000) return fail(BPGL_E_ARG, "onepass_cache_permille must be -1 (auto) or in [0, 1000]");
-        c->op_cache = (int)value;
-        c->op.cache_permille = op_cache_eff(c);
-        drop_graphs(c);
-        c->solver = false;
-        return 0;
-    }
-    if (!strcmp(key, "onepass_rows")) {
-        if (value < -1 || value > 1) return fail(BPGL_E_ARG, "onepass_rows must be -1 (auto), 0 or 1");
-        c->op_rows = (int)value;
-        if (c->op_shape) c->op.rilv = op_rows_eff(c);
-        drop_graphs(c);
-        c->solver = false;
-        return 0;
-    }
-    if (!strcmp(key, "onepass_sb1")) {
-        if (value < -1 || value > 0) return fail(BPGL_E_ARG, "onepass_sb1 must be -1 (auto) or 0");
-        c->op_sb1 = (int)value;
-        if (c->op_shape) c->op.rilv = op_rows_eff(c);
-        drop_graphs(c);
-        c->solver = false;
-        return 0;
-    }
-    if (!strcmp(key, "exchange_fp32")) {
-        if (value < -1 || value > 1) return fail(BPGL_E_ARG, "exchange_fp32 must be -1, 0 or 1");
-        c->xch32 = (int)value;
-        drop_graphs(c);
-        c->solver = false;
-        return 0;
-    }
-    if (!strcmp(key, "onepass_fail_at")) {   // test hook: the one-pass launch of iteration `value` fails once
-        c->op_fail_at = value < 0 ? -1 : value;
-        c->op.fail_at = c->op_fail_at;
-        drop_graphs(c);
-        c->solver = false;
-        return 0;
-    }
+    unsigned flags = kDropGraphs | kNeedsReset;
     if (!strcmp(key, "cus")) {   // size the persistent grids for this many CUs (the layout depends on it)
         if (c->bound) return fail(BPGL_E_STATE, "\"cus\" must be set before bpgl_bind (it sets the scratch layout)");
         if (value < 1 || value > c->dev_cus) return fail(BPGL_E_ARG, "cus must be in [1, %d]", c->dev_cus);
@@ -1318,34 +1152,29 @@ int bpgl_set_tuning(bpgl_ctx* c, const char* key, int64_t value) {
         geometry(c);
         return 0;
     }
-    if (!strcmp(key, "onepass_refresh")) {
-        if (value < 0) return fail(BPGL_E_ARG, "onepass_refresh must be >= 0");
-        c->op_refresh = (int)std::min<int64_t>(value, 1 << 30);
-        return 0;
+    if (!strcmp(key, "onepass_fail_at")) {   // test hook: the one-pass launch of iteration `value` fails once
+        c->op_fail_at = value < 0 ? -1 : value;
+    } else {
+        const Knob* k = std::find_if(std::begin(kKnobs), std::end(kKnobs), [&](const Knob& q) { return !strcmp(key, q.key); });
+        if (k == std::end(kKnobs)) return fail(BPGL_E_ARG, "unknown tuning key '%s'", key);
+        if (k->flags & kAnyNonZero) value = value != 0;
+        if (value < k->lo || value > k->hi || ((k->flags & kPowerOfTwo) && (value & (value - 1))))
+            return fail(BPGL_E_ARG, "%s must be %s", k->key, k->admissible);
+        if (k->flags & kClamp30) value = std::min<int64_t>(value, 1 << 30);
+        c->*k->member = (int)value;
+        flags = k->flags;
     }
-    if (!strcmp(key, "graph_max")) {   // speed only: the largest hipGraph of iterations (replays per run)
-        if (value < 1 || value > kGraphMaxIters || (value & (value - 1)))
-            return fail(BPGL_E_ARG, "graph_max must be a power of two in [1, %d]", kGraphMaxIters);
-        c->graph_max = (int)value;
-        drop_graphs(c);
-        c->solver = false;
-        return 0;
-    }
-    if (!strcmp(key, "nt_loads")) {
-        c->nt_loads = value != 0;
-        drop_graphs(c);
-        c->solver = false;
-        return 0;
-    }
-    return fail(BPGL_E_ARG, "unknown tuning key '%s'", key);
+    knob_mirrors(c);
+    if (flags & kDropGraphs) drop_graphs(c);
+    if (flags & kNeedsReset) c->solver = false;   // a new bpgl_solver_reset re-captures the iteration
+    return 0;
 }
 
 int bpgl_set_kernel_timing(bpgl_ctx* c, int enable) {
     if (!c) return fail(BPGL_E_ARG, "null context");
-    c->timing = enable != 0;
-    c->timed_iters = 0;
-    c->ref_timed = 0;
-    for (int k = 0; k < kTimedKinds; ++k) c->kind_used[k] = false;
+    c->tm.on = c->ref_tm.on = enable != 0;
+    c->tm.reset();
+    c->ref_tm.reset();
     return 0;
 }
 
@@ -1353,27 +1182,12 @@ int bpgl_kernel_times(bpgl_ctx* c, double* avg_ms, int64_t* samples) {
     if (!c || !avg_ms) return fail(BPGL_E_ARG, "null argument");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    double sum[kTimedKinds] = {0};
-    for (int64_t r = 0; r < c->ref_timed; ++r) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, c->ref_evs[2 * r], c->ref_evs[2 * r + 1]));
-        sum[8] += ms;
-    }
-    for (int64_t it = 0; it < c->timed_iters; ++it) {
-        for (int k = 0; k < kTimedKinds - 1; ++k) {
-            if (!c->kind_used[k]) continue;
-            float ms = 0.f;
-            const size_t i0 = 2 * ((size_t)it * kTimedKinds + k);
-            if (i0 + 1 >= c->evs.size()) continue;
-            HIP_TRY(hipEventElapsedTime(&ms, c->evs[i0], c->evs[i0 + 1]));
-            sum[k] += ms;
-        }
-    }
-    for (int k = 0; k < kTimedKinds; ++k) avg_ms[k] = c->timed_iters ? sum[k] / c->timed_iters : 0.0;
-    if (samples) *samples = c->timed_iters;
-    c->timed_iters = 0;
-    c->ref_timed = 0;
-    for (int k = 0; k < kTimedKinds; ++k) c->kind_used[k] = false;
+    int rc;
+    double refresh_ms = 0.0;
+    const int64_t iters = c->tm.iters;
+    if ((rc = c->ref_tm.sums(&refresh_ms)) || (rc = c->tm.collect(avg_ms, samples))) return rc;
+    avg_ms[kTimedKinds - 1] = iters ? refresh_ms / iters : 0.0;   // per iteration, as every other kind
+    c->ref_tm.reset();
     return 0;
 }
 

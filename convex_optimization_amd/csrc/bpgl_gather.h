@@ -4,7 +4,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #include "bpgl_device.h"
+#include "bpgl_host.h"
 
 namespace bpgl {
 
@@ -54,6 +57,33 @@ __global__ __launch_bounds__(kThreads) void k_gather_cols(GatherArgs a) {
         for (int e = 0; e < E; ++e) o.v[e] = off[e] >= 0 ? src[i * a.lda + off[e]] : (T)0;
         *reinterpret_cast<u32x4*>(dst + i * a.lda_out) = o.q;
     }
+}
+
+// Host side of both entry points: checks a.cols, a.n_out, a.out and a.lda_out (elements of `bytes`
+// bytes, one of BYTES...), then extra() (0, or the failure it reported), and launches about 4096 blocks:
+// each thread walks rows blockIdx.y, + gridDim.y, ... with its column offsets in registers.
+template <int... BYTES, typename Extra>
+int gather_columns(int device, hipStream_t stream, int bytes, const GatherArgs& a, Extra&& extra) {
+    using bpgl_host::fail;
+    if (!a.cols || !a.out) return fail(BPGL_E_ARG, "cols and A_out must be non-null");
+    const int V = 16 / bytes;
+    if (a.n_out <= 0) return fail(BPGL_E_ARG, "n_out must be > 0");
+    if (a.lda_out < a.n_out || a.lda_out % V)
+        return fail(BPGL_E_ARG, "lda_out (%lld) must be >= n_out (%lld) and a multiple of %d", a.lda_out, a.n_out, V);
+    if (((uintptr_t)a.out) % 16) return fail(BPGL_E_ARG, "A_out must be 16-byte aligned");
+    if (a.lda_out / V > (int64_t)0x7fffffff * kThreads) return fail(BPGL_E_ARG, "lda_out too large");
+    if (int rc = extra()) return rc;
+    HIP_TRY(hipSetDevice(device));
+    const int64_t gx = bpgl_host::cdiv(a.lda_out / V, kThreads);
+    const int64_t gy = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(a.m, 65535), bpgl_host::cdiv(4096, gx)));
+    const auto kernel = bpgl_host::dispatch<BYTES...>(bytes, [](auto b) { return &k_gather_cols<decltype(b)::value>; });
+    hipLaunchKernelGGL(kernel, dim3((unsigned)gx, (unsigned)gy), dim3(kThreads), 0, stream, a);
+    LAUNCH_CHECK("k_gather_cols");
+    return 0;
+}
+template <int... BYTES>
+int gather_columns(int device, hipStream_t stream, int bytes, const GatherArgs& a) {
+    return gather_columns<BYTES...>(device, stream, bytes, a, [] { return 0; });
 }
 
 }  // namespace bpgl

@@ -7,6 +7,8 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include <type_traits>
+#include <vector>
 
 #include "../../include/bpgl.h"
 
@@ -79,3 +81,100 @@ inline int usable_cus(hipStream_t s, int device) {
         hipError_t e_ = hipGetLastError();                                                   \
         if (e_ != hipSuccess) return bpgl_host::fail(BPGL_E_HIP, "launch %s: %s", what, hipGetErrorString(e_)); \
     } while (0)
+
+namespace bpgl_host {
+// f(std::integral_constant<int, V>{}) for the V among V0, Vs... that equals v (the last one when none
+// does): a run-time value picks a template argument, as static_for does on the device
+template <int V0, int... Vs, typename F>
+auto dispatch(int v, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) {
+        return f(std::integral_constant<int, V0>{});
+    } else {
+        if (v == V0) return f(std::integral_constant<int, V0>{});
+        return dispatch<Vs...>(v, f);
+    }
+}
+
+// HIP-event timing of the kernels of an iteration, KINDS kinds of them: event
+// 2 * (it * KINDS + kind) + {0: start, 1: end} of timed iteration `it` (the caller counts `iters`)
+// Hidden visibility: its member functions are weak symbols, and libbpgl.so exports none beyond its ABI.
+template <int KINDS>
+struct __attribute__((visibility("hidden"))) KernelTimes {
+    hipStream_t stream = nullptr;
+    bool on = false;
+    std::vector<hipEvent_t> evs;   // the context's destroy function destroys them
+    int64_t iters = 0;
+    bool kind_used[KINDS] = {};   // kinds recorded in the current window
+
+    void record(int64_t it, int kind, int end) {
+        kind_used[kind] = true;
+        const size_t idx = 2 * ((size_t)it * KINDS + kind) + end;
+        while (evs.size() <= idx) {
+            hipEvent_t e;
+            if (hipEventCreate(&e) != hipSuccess) return;
+            evs.push_back(e);
+        }
+        (void)hipEventRecord(evs[idx], stream);
+    }
+    // fn() between the two events of (it, kind); nothing but fn() when timing is off (graph capture relies
+    // on it), and no end event when fn fails
+    template <typename F>
+    int timed(int kind, int64_t it, F&& fn) {
+        if (!on) return fn();
+        record(it, kind, 0);
+        const int rc = fn();
+        if (!rc) record(it, kind, 1);
+        return rc;
+    }
+    void reset() {
+        iters = 0;
+        for (bool& u : kind_used) u = false;
+    }
+    // per kind, the time of the window's iterations; the stream must be idle
+    int sums(double* sum_ms) const {
+        for (int k = 0; k < KINDS; ++k) sum_ms[k] = 0.0;
+        for (int64_t it = 0; it < iters; ++it)
+            for (int k = 0; k < KINDS; ++k) {
+                const size_t i0 = 2 * ((size_t)it * KINDS + k);
+                if (!kind_used[k] || i0 + 1 >= evs.size()) continue;
+                float ms = 0.f;
+                HIP_TRY(hipEventElapsedTime(&ms, evs[i0], evs[i0 + 1]));
+                sum_ms[k] += ms;
+            }
+        return 0;
+    }
+    // ... averaged over the iterations; ends the window
+    int collect(double* avg_ms, int64_t* samples) {
+        if (int rc = sums(avg_ms)) return rc;
+        for (int k = 0; k < KINDS; ++k) avg_ms[k] = iters ? avg_ms[k] / iters : 0.0;
+        if (samples) *samples = iters;
+        reset();
+        return 0;
+    }
+};
+
+// enqueue() captured on `stream` as a hipGraph, instantiated into *exec and uploaded to the device, so
+// the first replay inside a caller's timed region pays no upload.  A failing enqueue() ends the
+// capture and returns its code.
+template <typename F>
+int capture_graph(hipStream_t stream, hipGraphExec_t* exec, F&& enqueue) {
+    hipGraph_t graph = nullptr;
+    hipError_t e = hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal);
+    if (e != hipSuccess)   // the text callers have always seen, whatever the stream is called here
+        return fail(BPGL_E_HIP, "hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal): %s",
+                    hipGetErrorString(e));
+    const int rc = enqueue();
+    e = hipStreamEndCapture(stream, &graph);
+    if (rc) {
+        if (graph) (void)hipGraphDestroy(graph);
+        return rc;
+    }
+    if (e != hipSuccess) return fail(BPGL_E_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
+    e = hipGraphInstantiate(exec, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    if (e != hipSuccess) return fail(BPGL_E_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
+    if ((e = hipGraphUpload(*exec, stream)) != hipSuccess)
+        return fail(BPGL_E_HIP, "hipGraphUpload: %s", hipGetErrorString(e));
+    return 0;
+}
+}  // namespace bpgl_host

@@ -37,10 +37,7 @@ struct bpgl_panel {
     bool own_stream = false, bound = false, have_diag = false, solver = false;
     PanelParams p{};
     hipGraphExec_t gexec = nullptr;
-    bool timing = false;
-    std::vector<hipEvent_t> evs;
-    int64_t timed_iters = 0;
-    bool kind_used[kPanelKinds] = {};   // kinds recorded in the current window (step: folded into reduce)
+    KernelTimes<kPanelKinds> tm;   // step: folded into reduce, never recorded
     int interleave[2] = {2, -1};  // mainloop variant per pass (tuning knobs; -1: the measured default, panel_ilv)
     int dsplit = 1;               // bf16 pieces of the solver's direction (d_split knob; 1 since round 4)
     int defer_x = 1;              // one block: x += gamma D' in the next pass-1 epilogue ("defer_x" knob; round 4 default)
@@ -68,17 +65,6 @@ struct bpgl_panel {
 
 namespace {
 
-// f(std::integral_constant<int, V>{}) for the V among V0, Vs... that equals v (the last one when none
-// does): a run-time value picks a template argument, as static_for does on the device
-template <int V0, int... Vs, typename F>
-auto dispatch(int v, F&& f) {
-    if constexpr (sizeof...(Vs) == 0) {
-        return f(std::integral_constant<int, V0>{});
-    } else {
-        if (v == V0) return f(std::integral_constant<int, V0>{});
-        return dispatch<Vs...>(v, f);
-    }
-}
 // NT, the 16-wide RHS tiles of the k right-hand sides (16, 32, 64 or 128: bpgl_panel_create)
 template <typename F>
 auto dispatch_nt(int k, F&& f) { return dispatch<1, 2, 4, 8>(k / 16, f); }
@@ -249,17 +235,6 @@ int panel_reduce(bpgl_panel* c, double* out, int mode) {
     LAUNCH_CHECK("k_panel_reduce");
     return 0;
 }
-void panel_ev(bpgl_panel* c, int64_t it, int kind, int end) {
-    if (!c->timing) return;
-    c->kind_used[kind] = true;
-    const size_t idx = 2 * ((size_t)it * kPanelKinds + kind) + end;
-    while (c->evs.size() <= idx) {
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) return;
-        c->evs.push_back(e);
-    }
-    (void)hipEventRecord(c->evs[idx], c->stream);
-}
 // exact: with the carried gradient, this iteration computes G = A^T R exactly (and stores it);
 // split_r: the update writes R's hi / lo images (with the carried gradient only the exact pass 1 reads
 // them, so only an iteration followed by an exact one needs to)
@@ -269,38 +244,30 @@ int panel_iteration(bpgl_panel* c, int64_t it, bool exact = false, bool split_r 
     // the update's carried-gradient operand: 0 none, 1 V = E + gamma S, 2 V = gamma S (G is exact now);
     // + 4: skip R's hi / lo images
     const int cflag = (c->gm_cur == 0 ? 0 : c->gm_cur == 1 ? 2 : 1) | (c->gm_cur && !split_r ? 4 : 0);
-    panel_ev(c, it, 0, 0);
-    rc = panel_pass(c, 0);
+    rc = c->tm.timed(0, it, [&] { return panel_pass(c, 0); });
     c->gm_cur = 0;
     if (rc) return rc;
-    panel_ev(c, it, 0, 1);
-    panel_ev(c, it, 1, 0);
-    if ((rc = panel_pass(c, 1))) return rc;
-    panel_ev(c, it, 1, 1);
-    panel_ev(c, it, 2, 0);
-    if (c->nblock == 1 && c->defer_x && c->fuse_update && c->fuse_ok) {   // reduce + line search + R update
-        rc = panel_reduce_upd(c, cflag);
-        panel_ev(c, it, 2, 1);
-        return rc;
-    }
-    if ((rc = panel_reduce(c, c->p.S, 1))) return rc;   // its last block per RHS runs the line search
-    panel_ev(c, it, 2, 1);
-    panel_ev(c, it, 4, 0);
-    if (c->nblock == 1 && c->defer_x) {   // R only; x += gamma D' rides on the next pass-1 epilogue (or the flush)
-        const dim3 ug((unsigned)std::min<int64_t>(cdiv((int64_t)c->k * c->m / 4, kThreads), 8192));
-        hipLaunchKernelGGL(k_panel_update1, ug, dim3(kThreads), 0, c->stream, c->p, cflag);
-    } else {
-        const int64_t n = (int64_t)c->k * c->w / 8 + (int64_t)c->k * c->m / 4;   // work units
-        const dim3 ug((unsigned)std::min<int64_t>(cdiv(n, kThreads), 8192));
-        const bool nb1 = c->nblock == 1;
-        const auto update = dispatch<1, 2>(c->dsplit, [&](auto ds) {
-            return nb1 ? &k_panel_update<decltype(ds)::value, true> : &k_panel_update<decltype(ds)::value, false>;
-        });
-        hipLaunchKernelGGL(update, ug, dim3(kThreads), 0, c->stream, c->p, cflag);
-    }
-    LAUNCH_CHECK("k_panel_update");
-    panel_ev(c, it, 4, 1);
-    return 0;
+    if ((rc = c->tm.timed(1, it, [&] { return panel_pass(c, 1); }))) return rc;
+    if (c->nblock == 1 && c->defer_x && c->fuse_update && c->fuse_ok)   // reduce + line search + R update
+        return c->tm.timed(2, it, [&] { return panel_reduce_upd(c, cflag); });
+    // its last block per RHS runs the line search
+    if ((rc = c->tm.timed(2, it, [&] { return panel_reduce(c, c->p.S, 1); }))) return rc;
+    return c->tm.timed(4, it, [&] {
+        if (c->nblock == 1 && c->defer_x) {   // R only; x += gamma D' rides on the next pass-1 epilogue (or the flush)
+            const dim3 ug((unsigned)std::min<int64_t>(cdiv((int64_t)c->k * c->m / 4, kThreads), 8192));
+            hipLaunchKernelGGL(k_panel_update1, ug, dim3(kThreads), 0, c->stream, c->p, cflag);
+        } else {
+            const int64_t n = (int64_t)c->k * c->w / 8 + (int64_t)c->k * c->m / 4;   // work units
+            const dim3 ug((unsigned)std::min<int64_t>(cdiv(n, kThreads), 8192));
+            const bool nb1 = c->nblock == 1;
+            const auto update = dispatch<1, 2>(c->dsplit, [&](auto ds) {
+                return nb1 ? &k_panel_update<decltype(ds)::value, true> : &k_panel_update<decltype(ds)::value, false>;
+            });
+            hipLaunchKernelGGL(update, ug, dim3(kThreads), 0, c->stream, c->p, cflag);
+        }
+        LAUNCH_CHECK("k_panel_update");
+        return 0;
+    });
 }
 // src [k][len] fp64 -> hi/lo images [k][ld]
 int panel_split(bpgl_panel* c, const double* src, int64_t len, int64_t ld, __bf16* hi, __bf16* lo, double sign,
@@ -408,6 +375,7 @@ int bpgl_panel_create(bpgl_panel** out, int device, int64_t m, int64_t n, int32_
         }
         c->own_stream = true;
     }
+    c->tm.stream = c->stream;
     *out = c;
     return 0;
 }
@@ -416,7 +384,7 @@ void bpgl_panel_destroy(bpgl_panel* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);   // destroy path: nothing to report to
     drop_graphs(c);
-    for (auto e : c->evs) (void)hipEventDestroy(e);
+    for (auto e : c->tm.evs) (void)hipEventDestroy(e);
     for (auto e : c->gap_ev)
         if (e) (void)hipEventDestroy(e);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
@@ -581,30 +549,21 @@ int bpgl_panel_reset_x0(bpgl_panel* c, const double* B, const double* mu, const 
     if (use_graph) {
         // kGraphIters iterations; with the carried gradient a second graph whose first iteration is
         // the exact one (bpgl_panel_step replays it at every g_period-th iteration)
-        for (int g = 0; g < (panel_carry(c) ? 2 : 1); ++g) {
-            hipGraph_t graph = nullptr;
-            const bool was = c->timing;
-            c->timing = false;
-            HIP_TRY(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-            rc = 0;
-            // R's images from the graph's last iteration: the next replay may start with the exact one
-            for (int k = 0; k < kGraphIters && !rc; ++k)
-                rc = panel_iteration(c, 0, g == 1 && k == 0, k == kGraphIters - 1);
-            hipError_t ec = hipStreamEndCapture(c->stream, &graph);
-            c->timing = was;
-            if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-            if (ec != hipSuccess) return fail(BPGL_E_HIP, "hipStreamEndCapture: %s", hipGetErrorString(ec));
-            hipGraphExec_t& ge = g ? c->gexec_ref : c->gexec;
-            hipError_t ei = hipGraphInstantiate(&ge, graph, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(graph);
-            if (ei != hipSuccess) return fail(BPGL_E_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ei));
-            // uploaded here, so the first replay in a caller's timed region pays no upload
-            if ((ei = hipGraphUpload(ge, c->stream)) != hipSuccess)
-                return fail(BPGL_E_HIP, "hipGraphUpload: %s", hipGetErrorString(ei));
-        }
+        const bool was = c->tm.on;
+        c->tm.on = false;
+        for (int g = 0; g < (panel_carry(c) ? 2 : 1) && !rc; ++g)
+            rc = capture_graph(c->stream, g ? &c->gexec_ref : &c->gexec, [&] {
+                int e = 0;
+                // R's images from the graph's last iteration: the next replay may start with the exact one
+                for (int k = 0; k < kGraphIters && !e; ++k)
+                    e = panel_iteration(c, 0, g == 1 && k == 0, k == kGraphIters - 1);
+                return e;
+            });
+        c->tm.on = was;
+        if (rc) return rc;
     }
     c->solver = true;
-    c->timed_iters = 0;
+    c->tm.iters = 0;
     return 0;
 }
 
@@ -617,17 +576,17 @@ int bpgl_panel_step(bpgl_panel* c, int64_t n_iter) {
     while (i < n_iter) {
         // carried gradient: every g_period-th iteration (the first included) computes G exactly
         const bool exact = panel_carry(c) && c->t_host % c->g_period == 0;
-        if (!c->timing && c->gexec && i + kGraphIters <= n_iter && c->t_host % kGraphIters == 0) {
+        if (!c->tm.on && c->gexec && i + kGraphIters <= n_iter && c->t_host % kGraphIters == 0) {
             HIP_TRY(hipGraphLaunch(exact ? c->gexec_ref : c->gexec, c->stream));
             c->n_exact += exact;
             i += kGraphIters;
             c->t_host += kGraphIters;
         } else {
             const bool next_exact = (c->t_host + 1) % c->g_period == 0;
-            if ((rc = panel_iteration(c, c->timing ? c->timed_iters : 0, exact, next_exact || i + 1 == n_iter)))
+            if ((rc = panel_iteration(c, c->tm.on ? c->tm.iters : 0, exact, next_exact || i + 1 == n_iter)))
                 return rc;
             c->n_exact += exact;
-            if (c->timing) c->timed_iters++;
+            if (c->tm.on) c->tm.iters++;
             ++i;
             ++c->t_host;
         }
@@ -663,8 +622,8 @@ const float* bpgl_panel_x(bpgl_panel* c) { return c ? c->p.X : nullptr; }
 
 int bpgl_panel_set_kernel_timing(bpgl_panel* c, int enable) {
     if (!c) return fail(BPGL_E_ARG, "null panel context");
-    c->timing = enable != 0;
-    c->timed_iters = 0;
+    c->tm.on = enable != 0;
+    c->tm.iters = 0;
     return 0;
 }
 
@@ -672,20 +631,7 @@ int bpgl_panel_kernel_times(bpgl_panel* c, double* avg_ms /* 5 */, int64_t* samp
     if (!c || !avg_ms) return fail(BPGL_E_ARG, "null argument");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    double sum[kPanelKinds] = {0};
-    for (int64_t it = 0; it < c->timed_iters; ++it)
-        for (int k = 0; k < kPanelKinds; ++k) {
-            if (!c->kind_used[k]) continue;
-            const size_t i0 = 2 * ((size_t)it * kPanelKinds + k);
-            float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, c->evs[i0], c->evs[i0 + 1]));
-            sum[k] += ms;
-        }
-    for (int k = 0; k < kPanelKinds; ++k) avg_ms[k] = c->timed_iters ? sum[k] / c->timed_iters : 0.0;
-    if (samples) *samples = c->timed_iters;
-    c->timed_iters = 0;
-    for (int k = 0; k < kPanelKinds; ++k) c->kind_used[k] = false;
-    return 0;
+    return c->tm.collect(avg_ms, samples);
 }
 
 int bpgl_panel_set_tuning(bpgl_panel* c, const char* key, int64_t value) {
@@ -832,27 +778,12 @@ int bpgl_panel_gap(bpgl_panel* c, double* G_all, double* R_fresh, uint8_t* keep,
 int bpgl_panel_gather_columns(bpgl_panel* c, const int32_t* cols, int64_t n_out, void* A_out, int64_t lda_out) {
     int rc;
     if ((rc = panel_ready(c))) return rc;
-    if (!cols || !A_out) return fail(BPGL_E_ARG, "cols and A_out must be non-null");
-    constexpr int V = 8;   // bf16 elements of a 16-byte piece
-    if (n_out <= 0) return fail(BPGL_E_ARG, "n_out must be > 0");
-    if (lda_out < n_out || lda_out % V)
-        return fail(BPGL_E_ARG, "lda_out (%lld) must be >= n_out (%lld) and a multiple of %d", (long long)lda_out,
-                    (long long)n_out, V);
-    if (((uintptr_t)A_out) % 16) return fail(BPGL_E_ARG, "A_out must be 16-byte aligned");
-    if (lda_out / V > (int64_t)0x7fffffff * kThreads) return fail(BPGL_E_ARG, "lda_out too large");
-    {   // A_out [m][lda_out] against the bound A [m][lda]
+    const GatherArgs a{c->p.A, c->p.lda, 0, c->n, c->n, c->m, cols, n_out, A_out, lda_out};
+    return gather_columns<2>(c->device, c->stream, 2, a, [&] {   // A_out [m][lda_out] against the bound A [m][lda]
         const uintptr_t a0 = (uintptr_t)c->p.A, a1 = a0 + 2 * (uintptr_t)((c->m - 1) * c->p.lda + c->n);
         const uintptr_t o0 = (uintptr_t)A_out, o1 = o0 + 2 * (uintptr_t)(c->m * lda_out);
-        if (o0 < a1 && a0 < o1) return fail(BPGL_E_ARG, "A_out overlaps the bound A");
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    GatherArgs a{c->p.A, c->p.lda, 0, c->n, c->n, c->m, cols, n_out, A_out, lda_out};
-    const int64_t gx = cdiv(lda_out / V, kThreads);
-    // about 4096 blocks; each thread walks rows blockIdx.y, + gridDim.y, ... with its column offsets in registers
-    const int64_t gy = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(c->m, 65535), cdiv(4096, gx)));
-    hipLaunchKernelGGL(k_gather_cols<2>, dim3((unsigned)gx, (unsigned)gy), dim3(kThreads), 0, c->stream, a);
-    LAUNCH_CHECK("k_gather_cols");
-    return 0;
+        return o0 < a1 && a0 < o1 ? fail(BPGL_E_ARG, "A_out overlaps the bound A") : 0;
+    });
 }
 
 int bpgl_panel_geometry(const bpgl_panel* c, int32_t* kchunks) {
