@@ -20,7 +20,9 @@ numpy fp64 restatement of the device's optimality certificate and screening rule
 ``panel_duality_gap``, the same per right-hand side of a panel, and ``mu_grid``, the geometric grid
 of a regularization path; ``kfold_masks``, ``masked_panel_iterate`` and ``masked_duality_gap``, the
 restatement of the panel's row-masked problems (K-fold cross-validation, DESIGN.md section 11);
-``compaction_columns``, the columns a screened panel keeps when it is compacted.
+``compaction_columns``, the columns a screened panel keeps when it is compacted (DESIGN.md section 12);
+``centred_diag``, ``intercept_panel_iterate`` and ``intercept_duality_gap``, the restatement of the
+panel's intercept.
 """
 import numpy as np
 
@@ -207,6 +209,90 @@ def masked_duality_gap(A, b, w, x, mu, diag=None):
     score = scale * np.abs(g) + np.sqrt(dg) * np.sqrt(2.0 * np.maximum(gap, 0.0))
     return dict(primal=primal, dual=dual, gap=gap, scale=scale, gnorm_inf=gn, holdout_sse=float(h @ h),
                 score=score, keep=~(score < mu), g=g, r=r)
+
+
+# ---------------------------------------------------------------------------
+# Intercept: min over x, beta0 of 1/2 || w o (A x + beta0 - b) ||^2 + mu ||x||_1.
+# beta0 is profiled out: the objective is 1/2 || P_w (A x - b) ||^2 + mu ||x||_1 with
+# P_w v = w o (v - (w . v) / n_w), and the iteration carries the centred residual.  The host restatement
+# of bpgl_panel_set_intercept's solver and certificate.
+# ---------------------------------------------------------------------------
+def _centre(w, v):
+    """P_w v = w o (v - mean of v over the rows with w = 1); 0 when w has no such row."""
+    nw = float(w.sum())
+    return w * (v - (float(w @ v) / nw if nw > 0 else 0.0))
+
+
+def centred_diag(A):
+    """d_j = sum_i (a_ij - mean_j)^2 over all rows, (n,): the diag of the intercept's shrink and screen.
+    d_j >= || P_w a_j ||^2 for every 0/1 w, so one d serves every fold.  The deviations are taken from
+    the column's first entry, so a constant column gives exactly 0."""
+    A = np.asarray(A, dtype=np.float64)
+    dev = A - A[:1]
+    return np.square(dev - dev.sum(axis=0) / A.shape[0]).sum(axis=0)
+
+
+def intercept_panel_iterate(A, b, w, mu, iters, diag=None, x0=None):
+    """``iters`` updates (one feature block) of the panel's iteration with the intercept on one
+    right-hand side, in fp64: R = P_w (A x - b), G = A^T R, the shrink with ``diag`` (default
+    ``centred_diag(A)``; a column with d_j = 0 keeps x_j = 0), S = w o (A D), c = sum S / n_w, the exact
+    line search gamma = clip(-(R.S + mu (|x + D|_1 - |x|_1)) / (S.S - c sum S), 0, 1) (0 when the
+    curvature is <= 0), x += gamma D and R += gamma w o (S - c).  Returns dict(x, r, intercept) with
+    intercept = -mean over the in-rows of (A x - b)."""
+    A = np.asarray(A, dtype=np.float64)
+    n = A.shape[1]
+    b = np.asarray(b, dtype=np.float64).reshape(-1)
+    w = (np.asarray(w).reshape(-1) != 0).astype(np.float64)
+    nw = float(w.sum())
+    mu = float(mu)
+    dg = centred_diag(A) if diag is None else np.asarray(diag, dtype=np.float64).reshape(-1)
+    with np.errstate(divide="ignore"):
+        rec = np.where(dg > 0, 1.0 / dg, 0.0)
+    x = np.zeros(n) if x0 is None else np.array(x0, dtype=np.float64).reshape(-1)
+    R = _centre(w, A @ x - b)
+    for _ in range(int(iters)):
+        g = A.T @ R
+        rx = dg * x - g
+        Bx = rec * (np.sign(rx) * np.maximum(np.abs(rx) - mu, 0))
+        D = Bx - x
+        s = w * (A @ D)
+        sm = float(s.sum())
+        c = sm / nw if nw > 0 else 0.0
+        r1 = R @ s + mu * (np.abs(Bx).sum() - np.abs(x).sum())
+        r2 = s @ s - c * sm
+        gamma = 0.0 if r2 <= 0 else float(np.clip(-r1 / r2, 0, 1))
+        x += gamma * D
+        R += gamma * w * (s - c)
+    e = A @ x - b
+    return dict(x=x, r=R, intercept=-(float(w @ e) / nw) if nw > 0 else 0.0)
+
+
+def intercept_duality_gap(A, b, w, x, mu, diag=None):
+    """``masked_duality_gap`` on the profiled problem: with e = A x - b and c = the in-row mean of e,
+    r = w o (e - c) (it sums to zero over the in-rows: the intercept's dual constraint), g = A^T r,
+    primal, dual, gap, scale, gnorm_inf from them; intercept = -c; holdout_sse = the held-out sum of
+    (a_i . x + intercept - b_i)^2; score and keep with ``diag`` (default ``centred_diag(A)``)."""
+    A = np.asarray(A, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64).reshape(-1)
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    w = (np.asarray(w).reshape(-1) != 0).astype(np.float64)
+    nw = float(w.sum())
+    mu = float(mu)
+    e = A @ x - b
+    c = float(w @ e) / nw if nw > 0 else 0.0
+    r = w * (e - c)
+    g = A.T @ r
+    rr = float(r @ r)
+    primal = 0.5 * rr + mu * float(np.abs(x).sum())
+    gn = float(np.max(np.abs(g)))
+    scale = min(1.0, mu / gn) if gn > 0.0 else 1.0
+    dual = -0.5 * scale * scale * rr - scale * float(r @ b)
+    gap = primal - dual
+    h = (1.0 - w) * (e - c)
+    dg = centred_diag(A) if diag is None else np.asarray(diag, dtype=np.float64).reshape(-1)
+    score = scale * np.abs(g) + np.sqrt(dg) * np.sqrt(2.0 * np.maximum(gap, 0.0))
+    return dict(primal=primal, dual=dual, gap=gap, scale=scale, gnorm_inf=gn, holdout_sse=float(h @ h),
+                intercept=-c if nw > 0 else 0.0, score=score, keep=~(score < mu), g=g, r=r)
 
 
 # ---------------------------------------------------------------------------

@@ -111,6 +111,10 @@ struct PanelParams {
     unsigned long long* lsdone;  // line searches finished (monotone, + k per launch): the last one bumps t
     // row mask (bpgl_panel_set_row_mask): only the masked (MK) kernel variants read it
     const unsigned char* W;      // [k][m] nonzero: the row is in that RHS's objective; null without a mask
+    // intercept (bpgl_panel_set_intercept): only the intercept (IC) kernel variants read these
+    double* lss;        // [m / kLspRows][k]  line-search partials: sum s (beside lsp's r.s, s.s)
+    double* cshift;     // [k]  c = sum s / n_w of the last line search, published beside gamma
+    const double* nw;   // [k]  rows in each RHS's objective (0 for an all-zero mask column)
 };
 
 // a thread's 4 consecutive rows of a masked RHS: the slab sums of held-out rows become 0 by select
@@ -118,6 +122,13 @@ struct PanelParams {
 __device__ __forceinline__ void panel_mask4(unsigned wv, double (&s)[4]) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) s[q] = ((wv >> (8 * q)) & 0xffu) ? s[q] : 0.0;
+}
+
+// intercept: the same 4 rows of the masked S as the centred P_w s -- s - c at the in-rows, 0 (by select) at
+// the held-out ones -- which is what the R update and the carried operand take
+__device__ __forceinline__ void panel_centre4(unsigned wv, double c, double (&s)[4]) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) s[q] = ((wv >> (8 * q)) & 0xffu) ? s[q] - c : 0.0;
 }
 
 constexpr int kLspRows = 1024;    // rows per line-search partial
@@ -901,7 +912,8 @@ __device__ __forceinline__ double panel_ld_sc1(const double* q) {
     return __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<const unsigned long long*>(q),
                                                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }
-template <bool LSP_SC1> __device__ void panel_step_rhs(const PanelParams& p, int rhs, double a, double b, double e);
+template <bool LSP_SC1, bool IC = false>
+__device__ void panel_step_rhs(const PanelParams& p, int rhs, double a, double b, double e);
 // this thread's share of the pass-1 norm partials of one RHS (tiles q = threadIdx.x, + kThreads, ...):
 // sum |Bx|, sum |x|, max err -- loaded by every k_panel_reduce block before its slab loads, so the last
 // block's line search does not wait for them
@@ -977,14 +989,40 @@ __device__ __forceinline__ unsigned long long panel_publish_partials(const Panel
     return __hip_atomic_fetch_add(p.cnt + rhs, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// intercept: the third line-search partial, sum s of the (masked) 4 rows, summed over each wave like the
+// other two ...
+__device__ __forceinline__ void panel_sum_waves(const double (&s)[4], double (&sm)[kWaves]) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const double t = wave_sum(((s[0] + s[1]) + s[2]) + s[3]);
+    if (lane == 0) sm[wave] = t;
+}
+// the block's LDS rows for it: behind a function, so that only the IC variants that call it hold them
+template <int U>
+__device__ __forceinline__ double (&panel_sum_rows())[U][kWaves] {
+    __shared__ double sm[U][kWaves];
+    return sm;
+}
+// ... and published by thread 0 (the 4 waves added in order) to p.lss, sc1, just before panel_publish_partials,
+// whose wait and arrival cover these stores as they cover its own
+template <int U>
+__device__ __forceinline__ void panel_publish_sums(const PanelParams& p, int rhs, int grp0,
+                                                   const double (&sm)[U][kWaves]) {
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+        panel_st_sc1(p.lss + (long long)(grp0 + u) * p.k + rhs, ((sm[u][0] + sm[u][1]) + sm[u][2]) + sm[u][3]);
+}
+
 // S = sum over chunks (fp64, fixed order); line-search partials per RHS and
 // 1024-row group (mode 1), or plain output (mode 0, API).  grid = k x (m / 1024);
 // a thread owns 4 consecutive rows (16-B slab loads).  Mode 1: the last block of an RHS to
 // finish runs that RHS's line search (panel_step_rhs), so no separate step launch.
 // MK (mode 1 only): the masked fold -- S becomes w o S (panel_mask4) before it is stored and before
 // the line-search partials, so the update kernels see the masked S and need no mask of their own.
-template <bool MK>
+// IC (with MK, mode 1): the intercept's third partial, sum s of the masked S per group, and the line search
+// that uses it (panel_step_rhs<true, true>); S is stored masked but uncentred (k_panel_update1<true> centres).
+template <bool MK, bool IC = false>
 __global__ __launch_bounds__(kThreads) void k_panel_reduce(PanelParams p, double* __restrict__ Sout, int mode) {
+    static_assert(!IC || MK, "the intercept runs on the masked fold");
     const int rhs = blockIdx.x % p.k;
     const int grp = blockIdx.x / p.k;
     const long long i = (long long)grp * kLspRows + 4 * threadIdx.x;
@@ -1009,6 +1047,9 @@ __global__ __launch_bounds__(kThreads) void k_panel_reduce(PanelParams p, double
             const double r[4] = {r01.x, r01.y, r23.x, r23.y};
             panel_ls_partial4(r, s, rs, ss);
         }
+        if constexpr (IC) panel_sum_waves(s, panel_sum_rows<1>()[0]);   // whole waves are in or out: m % 256 == 0
+    } else if constexpr (IC) {
+        if ((threadIdx.x & 63) == 0) panel_sum_rows<1>()[0][threadIdx.x >> 6] = 0.0;
     }
     if (!mode) return;
     __shared__ double sr[1][kWaves], sq[1][kWaves];
@@ -1017,17 +1058,21 @@ __global__ __launch_bounds__(kThreads) void k_panel_reduce(PanelParams p, double
     __shared__ int last;
     if (threadIdx.x == 0) {
         const unsigned long long ng = (unsigned long long)((p.m + kLspRows - 1) / kLspRows);
+        if constexpr (IC) panel_publish_sums<1>(p, rhs, grp, panel_sum_rows<1>());
         last = ((panel_publish_partials<1>(p, rhs, grp, sr, sq) + 1) % ng) == 0;
     }
     __syncthreads();
-    if (last) panel_step_rhs<true>(p, rhs, na, nb, ne);
+    if (last) panel_step_rhs<true, IC>(p, rhs, na, nb, ne);
 }
 
 // per-RHS line search (lasso.py:129-136): the pass-1 norm partials and the reduce's r.s / s.s
 // partials of one RHS folded in a fixed order -> gamma, err.  LSP_SC1: read the line-search
 // partials write-through (they were written by other blocks of the running launch).
 // a, b, e: this thread's share of the norm partials (panel_norm_share)
-template <bool LSP_SC1>
+// IC (the intercept): the sum-s partials folded in the same group order; with
+// c = sum s / n_w the curvature is |P_w s|^2 = s.s - c sum s (r.s needs no correction: r is centred), gamma = 0
+// when that is <= 0, and c is published beside gamma for the update
+template <bool LSP_SC1, bool IC>
 __device__ void panel_step_rhs(const PanelParams& p, int rhs, double a, double b, double e) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     __shared__ double s3[3][kWaves];
@@ -1039,7 +1084,8 @@ __device__ void panel_step_rhs(const PanelParams& p, int rhs, double a, double b
     // thread), summed by thread 0 in group order -- a serial chain of dependent loads cost ~1 us
     // per group
     __shared__ double lsr[kThreads][2];
-    double rs = 0.0, ss = 0.0;
+    __shared__ double lsm[IC ? kThreads : 1];
+    double rs = 0.0, ss = 0.0, sm = 0.0;
     const int ng = (int)((p.m + kLspRows - 1) / kLspRows);
     for (int g0 = 0; g0 < ng; g0 += kThreads) {
         const int g = g0 + (int)threadIdx.x;
@@ -1047,10 +1093,18 @@ __device__ void panel_step_rhs(const PanelParams& p, int rhs, double a, double b
             const double* q = p.lsp + ((long long)g * p.k + rhs) * 2;
             lsr[threadIdx.x][0] = LSP_SC1 ? panel_ld_sc1(q) : q[0];
             lsr[threadIdx.x][1] = LSP_SC1 ? panel_ld_sc1(q + 1) : q[1];
+            if constexpr (IC) {
+                const double* qm = p.lss + (long long)g * p.k + rhs;
+                lsm[threadIdx.x] = LSP_SC1 ? panel_ld_sc1(qm) : qm[0];
+            }
         }
         __syncthreads();
         if (threadIdx.x == 0)
             for (int i = 0; i < kThreads && g0 + i < ng; ++i) { rs += lsr[i][0]; ss += lsr[i][1]; }
+        if constexpr (IC) {
+            if (threadIdx.x == 0)
+                for (int i = 0; i < kThreads && g0 + i < ng; ++i) sm += lsm[i];
+        }
         __syncthreads();
     }
     if (threadIdx.x == 0) {
@@ -1060,7 +1114,15 @@ __device__ void panel_step_rhs(const PanelParams& p, int rhs, double a, double b
         for (int q = 1; q < kWaves; ++q) e = nan_max(e, s3[2][q]);
         const double r1 = rs + p.mu[rhs] * (a - b);
         // write-through: k_panel_reduce_upd's other blocks read them in the same launch
-        panel_st_sc1(p.gamma + rhs, (ss == 0.0) ? 0.0 : proj(-r1 / ss, 0.0, 1.0));
+        if constexpr (IC) {
+            const double nw = p.nw[rhs];
+            const double c = nw > 0.0 ? sm / nw : 0.0;   // an all-zero mask column: s = 0, gamma = 0
+            const double ssc = ss - c * sm;
+            panel_st_sc1(p.gamma + rhs, (ssc <= 0.0) ? 0.0 : proj(-r1 / ssc, 0.0, 1.0));
+            panel_st_sc1(p.cshift + rhs, c);
+        } else {
+            panel_st_sc1(p.gamma + rhs, (ss == 0.0) ? 0.0 : proj(-r1 / ss, 0.0, 1.0));
+        }
         panel_st_sc1(p.err_rhs + rhs, e);
         if (rhs == 0) p.st->cur_mb = p.st->t % p.nblock;   // nobody else reads it in this launch
     }
@@ -1209,6 +1271,9 @@ __global__ __launch_bounds__(kThreads) void k_panel_update(PanelParams p, int cf
 // One feature block: R_j += gamma_j S_j (= Ax_j + gamma_j S_j - B_j; Ax is not kept) and its
 // hi/lo split; x += gamma D' is left pending for the next pass-1 epilogue (or k_panel_flush).
 // A thread owns 4 consecutive residual rows.  Also bumps t.
+// IC (the intercept): the stored S is the masked one; the rows' mask word and the line search's c make
+// it P_w s (panel_centre4) before the same update.
+template <bool IC = false>
 __global__ __launch_bounds__(kThreads) void k_panel_update1(PanelParams p, int cflag) {
     const long long nr = (long long)p.k * p.m;
     const unsigned ur = (unsigned)(nr / 4), m4 = (unsigned)(p.m / 4);
@@ -1221,7 +1286,9 @@ __global__ __launch_bounds__(kThreads) void k_panel_update1(PanelParams p, int c
         const double2 r23 = *reinterpret_cast<const double2*>(p.R + e + 2);
         const double2 s01 = *reinterpret_cast<const double2*>(p.S + e);
         const double2 s23 = *reinterpret_cast<const double2*>(p.S + e + 2);
-        const double r[4] = {r01.x, r01.y, r23.x, r23.y}, s[4] = {s01.x, s01.y, s23.x, s23.y};
+        const double r[4] = {r01.x, r01.y, r23.x, r23.y};
+        double s[4] = {s01.x, s01.y, s23.x, s23.y};
+        if constexpr (IC) panel_centre4(*reinterpret_cast<const unsigned*>(p.W + e), p.cshift[rhs], s);
         panel_r_update4(p, cflag, e, re, g, r, s, panel_carry_e(p, cflag, e));
     }
     if (blockIdx.x == 0 && threadIdx.x < 64) panel_bump_t<false>(p, true);
@@ -1244,9 +1311,13 @@ __global__ __launch_bounds__(kThreads) void k_panel_update1(PanelParams p, int c
 // MK: the masked fold of k_panel_reduce<true> (one 32-bit word of 4 mask bytes per 1024-row group,
 // S zeroed by select before the partials, the carried operand and the R update); same grid, waits
 // and failure path.
+// IC (with MK; the intercept): k_panel_reduce<true, true>'s third partial per group; the RHS's last block
+// publishes c beside gamma before `ready`, the waiting blocks read it where they read gamma, and every block
+// turns its masked S into P_w s (panel_centre4, from the mask words it kept) before the update.
 constexpr unsigned kPanelPolls = 1u << 20;
-template <int U, bool MK = false>
+template <int U, bool MK = false, bool IC = false>
 __global__ __launch_bounds__(kThreads) void k_panel_reduce_upd(PanelParams p, int cflag, int G) {
+    static_assert(!IC || MK, "the intercept runs on the masked fold");
     const int rhs = blockIdx.x % p.k;
     const int g = blockIdx.x / p.k;
     double na = 0.0, nb = 0.0, ne = 0.0;
@@ -1254,6 +1325,7 @@ __global__ __launch_bounds__(kThreads) void k_panel_reduce_upd(PanelParams p, in
     const long long cstride = (long long)p.k * p.m;
     double s[U][4], r[U][4];
     float4 ev[U];
+    unsigned wk[U];   // (IC) the groups' mask words, kept for the centring
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const long long e = (long long)rhs * p.m + (long long)(g * U + u) * kLspRows + 4 * threadIdx.x;
@@ -1266,6 +1338,7 @@ __global__ __launch_bounds__(kThreads) void k_panel_reduce_upd(PanelParams p, in
         const double4 t = panel_slab_sum4(p.Sslab + e, cstride, p.kchunks);
         s[u][0] = t.x; s[u][1] = t.y; s[u][2] = t.z; s[u][3] = t.w;
         if constexpr (MK) panel_mask4(wv, s[u]);
+        if constexpr (IC) wk[u] = wv;
     }
     // per-group line-search partials, in k_panel_reduce's order
     __shared__ double sr[U][kWaves], sq[U][kWaves];
@@ -1275,11 +1348,16 @@ __global__ __launch_bounds__(kThreads) void k_panel_reduce_upd(PanelParams p, in
         panel_ls_partial4(r[u], s[u], rs, ss);
         panel_ls_waves(rs, ss, sr[u], sq[u]);
     }
+    if constexpr (IC) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) panel_sum_waves(s[u], panel_sum_rows<U>()[u]);
+    }
     __syncthreads();
     __shared__ int last, ok;
     __shared__ unsigned long long target;
-    __shared__ double gsh;
+    __shared__ double gsh, csh;
     if (threadIdx.x == 0) {
+        if constexpr (IC) panel_publish_sums<U>(p, rhs, g * U, panel_sum_rows<U>());
         const unsigned long long old = panel_publish_partials<U>(p, rhs, g * U, sr, sq);
         last = ((old + 1) % (unsigned long long)G) == 0;
         target = (old / (unsigned long long)G + 1) * (unsigned long long)G;
@@ -1287,9 +1365,10 @@ __global__ __launch_bounds__(kThreads) void k_panel_reduce_upd(PanelParams p, in
     }
     __syncthreads();
     if (last) {
-        panel_step_rhs<true>(p, rhs, na, nb, ne);   // gamma, err_rhs (sc1)
+        panel_step_rhs<true, IC>(p, rhs, na, nb, ne);   // gamma, err_rhs (and c) (sc1)
         if (threadIdx.x == 0) {
             gsh = panel_ld_sc1(p.gamma + rhs);
+            if constexpr (IC) csh = panel_ld_sc1(p.cshift + rhs);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __hip_atomic_store(p.ready + rhs, target, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const unsigned long long d = __hip_atomic_fetch_add(p.lsdone, 1ull, __ATOMIC_RELAXED,
@@ -1302,7 +1381,10 @@ __global__ __launch_bounds__(kThreads) void k_panel_reduce_upd(PanelParams p, in
             if (n-- == 0) { ok = 0; break; }
             __builtin_amdgcn_s_sleep(2);
         }
-        if (ok) gsh = panel_ld_sc1(p.gamma + rhs);
+        if (ok) {
+            gsh = panel_ld_sc1(p.gamma + rhs);
+            if constexpr (IC) csh = panel_ld_sc1(p.cshift + rhs);
+        }
         else __hip_atomic_store(reinterpret_cast<unsigned long long*>(&p.st->fail), 1ull, __ATOMIC_RELAXED,
                                 __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -1313,6 +1395,7 @@ __global__ __launch_bounds__(kThreads) void k_panel_reduce_upd(PanelParams p, in
     for (int u = 0; u < U; ++u) {
         const long long e = (long long)rhs * p.m + (long long)(g * U + u) * kLspRows + 4 * threadIdx.x;
         const long long re = (long long)rhs * p.ldr + (e - (long long)rhs * p.m);
+        if constexpr (IC) panel_centre4(wk[u], csh, s[u]);
         panel_r_update4(p, cflag, e, re, gm, r[u], s[u], ev[u]);
     }
     // every RHS's err_rhs is published (sc1): end the iteration
@@ -1343,6 +1426,47 @@ __global__ __launch_bounds__(kThreads) void k_panel_mask_b(const double* __restr
         const bool in = W[e] != 0;
         Bw[e] = in ? v : 0.0;
         Bh[e] = in ? 0.0 : v;
+    }
+}
+
+// per RHS (one block each): n_w, the rows in its objective (an integer count: exact in any order)
+__global__ __launch_bounds__(kThreads) void k_panel_count_rows(const unsigned char* __restrict__ W, long long m,
+                                                               double* __restrict__ nw) {
+    const int k = blockIdx.x;
+    long long s = 0;
+    for (long long i = threadIdx.x; i < m; i += kThreads) s += W[(long long)k * m + i] != 0;
+    __shared__ long long red[kThreads];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    long long tot = 0;
+    for (int q = 0; q < kThreads; ++q) tot += red[q];
+    nw[k] = (double)tot;
+}
+
+// reset with the intercept (one block per RHS): bmean = the mean of B over the in-rows (a thread's rows in
+// index order, wave sums, the 4 waves in order), then Bw = P_w B = b - bmean at the in-rows, 0 at the others
+// (so R0 = -P_w B), and Bh = (1 - w) o B as k_panel_mask_b leaves it
+__global__ __launch_bounds__(kThreads) void k_panel_centre_b(const double* __restrict__ B,
+                                                             const unsigned char* __restrict__ W, long long m,
+                                                             const double* __restrict__ nw, double* __restrict__ Bw,
+                                                             double* __restrict__ Bh, double* __restrict__ bmean) {
+    const long long k0 = (long long)blockIdx.x * m;
+    double s = 0.0;
+    for (long long i = threadIdx.x; i < m; i += kThreads) s += W[k0 + i] != 0 ? B[k0 + i] : 0.0;
+    s = wave_sum(s);
+    __shared__ double red[kWaves];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) red[wave] = s;
+    __syncthreads();
+    const double n = nw[blockIdx.x];
+    const double mean = n > 0.0 ? (((red[0] + red[1]) + red[2]) + red[3]) / n : 0.0;
+    if (threadIdx.x == 0) bmean[blockIdx.x] = mean;
+    for (long long i = threadIdx.x; i < m; i += kThreads) {
+        const double v = B[k0 + i];
+        const bool in = W[k0 + i] != 0;
+        Bw[k0 + i] = in ? v - mean : 0.0;
+        Bh[k0 + i] = in ? 0.0 : v;
     }
 }
 
@@ -1384,6 +1508,51 @@ __global__ __launch_bounds__(kThreads) void k_panel_diag(PanelParams p, double* 
         const double s = ((part[0][c] + part[1][c]) + part[2][c]) + part[3][c];
         diag[blockIdx.x * 512 + c] = s;
         rec[blockIdx.x * 512 + c] = 1.0 / s;
+    }
+}
+
+// the intercept's diag: d_j = sum_i (a_ij - mean_j)^2 over all rows, k_panel_diag's tiling.  Two walks: the
+// column means first (fp64, the same fixed-order combine), then the squared deviations -- not
+// sum a^2 - (sum a)^2 / m, which does not give an exact 0 for a constant column.  (m copies of one bf16 value
+// add up exactly in fp64 and divide back to it, so a constant column has d = 0 exactly.)  rec = 0 where d = 0:
+// the shrink then leaves that x at 0, which is optimal -- the intercept absorbs the column.
+__global__ __launch_bounds__(kThreads) void k_panel_diag_centred(PanelParams p, double* __restrict__ diag,
+                                                                 double* __restrict__ rec) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long n = (long long)p.nblock * p.w;
+    const long long col = (long long)blockIdx.x * 512 + lane * 8;
+    __shared__ double part[kWaves][512];
+    __shared__ double mean[512];
+    double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (long long i = wave; i < p.m && col < n; i += kWaves) {
+        const bf16x8 v = *reinterpret_cast<const bf16x8*>(p.A + i * p.lda + col);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] += (double)(float)v[e];
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) part[wave][lane * 8 + e] = acc[e];
+    __syncthreads();
+    for (int c = threadIdx.x; c < 512; c += kThreads)
+        mean[c] = (((part[0][c] + part[1][c]) + part[2][c]) + part[3][c]) / (double)p.m;
+    __syncthreads();
+    double mu[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { mu[e] = mean[lane * 8 + e]; acc[e] = 0.0; }
+    for (long long i = wave; i < p.m && col < n; i += kWaves) {
+        const bf16x8 v = *reinterpret_cast<const bf16x8*>(p.A + i * p.lda + col);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const double d = (double)(float)v[e] - mu[e];
+            acc[e] = fma(d, d, acc[e]);
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) part[wave][lane * 8 + e] = acc[e];
+    __syncthreads();
+    for (int c = threadIdx.x; c < 512 && blockIdx.x * 512LL + c < n; c += kThreads) {
+        const double s = ((part[0][c] + part[1][c]) + part[2][c]) + part[3][c];
+        diag[blockIdx.x * 512 + c] = s;
+        rec[blockIdx.x * 512 + c] = s > 0.0 ? 1.0 / s : 0.0;
     }
 }
 

@@ -26,7 +26,7 @@ constexpr int kPanelKinds = 5;   // pass1, pass2, reduce, step, update
 // byte offsets of the scratch regions (panel_layout), in the order they are laid out
 struct PanelLayout {
     int64_t st, Rh, Rl, Dh, Dl, X, Ax, B, R, diag, rec, Sslab, S, norms, lsp, mu, gamma, err_rhs, cnt, ready, lsdone, Gc,
-        Sh, Ec, At, A1t, gpart, gparts, gcounts, gres, W, Bh, ghold, total;
+        Sh, Ec, At, A1t, gpart, gparts, gcounts, gres, W, Bh, ghold, lss, cshift, nw, bmean, gipart, gicp, total;
 };
 
 struct bpgl_panel {
@@ -54,7 +54,11 @@ struct bpgl_panel {
     int64_t n_exact = 0;          // carried gradient: exact-gradient iterations since the last reset
     hipEvent_t gap_ev[3] = {};    // bpgl_panel_gap: before product 1, between the products, after product 2
     int64_t gap_ns[2] = {};       // the last call's two products (each with its fold), stats "gap_prod1_ns" / "gap_prod2_ns"
-    bool masked = false;          // bpgl_panel_set_row_mask installed a mask: the MK kernel variants run
+    bool masked = false;          // a mask is installed (the caller's, or the intercept's all-ones one): the MK kernel variants run
+    bool user_mask = false;       // ... and it is the caller's (bpgl_panel_set_row_mask)
+    bool icpt = false;            // bpgl_panel_set_intercept: the intercept (IC) kernel variants run (always with `masked`)
+    bool icpt_valid = false;      // a bpgl_panel_gap has run since the last reset: icpt_host is its beta0
+    std::vector<double> icpt_host;
     char* scratch = nullptr;      // the caller's scratch and its layout (bpgl_panel_bind)
     PanelLayout L{};
     template <typename T>
@@ -87,9 +91,16 @@ int pgap_prod(bpgl_panel* c, const PanelGapArgs& a, dim3 grid) {
     hipLaunchKernelGGL(prod, grid, blk, 0, c->stream, a);
     LAUNCH_CHECK("k_pgap_prod");
     const dim3 fgrid((unsigned)cdiv((int64_t)c->k * (PROD == 1 ? c->m : c->n), kThreads));
-    if (PROD == 1 && c->masked) hipLaunchKernelGGL((k_pgap_fold<1, true>), fgrid, blk, 0, c->stream, a);
+    if (PROD == 1 && c->icpt) hipLaunchKernelGGL((k_pgap_fold<1, true, true>), fgrid, blk, 0, c->stream, a);
+    else if (PROD == 1 && c->masked) hipLaunchKernelGGL((k_pgap_fold<1, true>), fgrid, blk, 0, c->stream, a);
     else hipLaunchKernelGGL((k_pgap_fold<PROD, false>), fgrid, blk, 0, c->stream, a);
     LAUNCH_CHECK("k_pgap_fold");
+    if (PROD == 1 && c->icpt) {   // the fold left the uncentred e: its in-row mean per RHS, then P_w e and the held-out squares
+        hipLaunchKernelGGL(k_pgap_icpt_mean, dim3((unsigned)c->k), blk, 0, c->stream, a, (long long)(c->m / kThreads));
+        LAUNCH_CHECK("k_pgap_icpt_mean");
+        hipLaunchKernelGGL(k_pgap_centre, fgrid, blk, 0, c->stream, a);
+        LAUNCH_CHECK("k_pgap_centre");
+    }
     return 0;
 }
 PanelLayout panel_layout(const bpgl_panel* c) {
@@ -140,6 +151,14 @@ PanelLayout panel_layout(const bpgl_panel* c) {
     L.W = k.take(km);
     L.Bh = k.take(8 * km);
     L.ghold = k.take(8 * (km / kThreads));
+    // the intercept (bpgl_panel_set_intercept): the line search's sum-s partials and c, the in-row counts, the
+    // in-row means of b, and the certificate's in-row partials and its c' / beta0.  Again after everything else.
+    L.lss = k.take(8 * cdiv(c->m, kLspRows) * c->k);
+    L.cshift = k.take(8 * (int64_t)c->k);
+    L.nw = k.take(8 * (int64_t)c->k);
+    L.bmean = k.take(8 * (int64_t)c->k);
+    L.gipart = k.take(8 * (km / kThreads));
+    L.gicp = k.take(8 * 2 * (int64_t)c->k);
     L.total = k.off;
     return L;
 }
@@ -198,28 +217,30 @@ bool panel_fused_geo(const bpgl_panel* c, int* G, int* U) {
 // the k_panel_reduce_upd variant of a geometry: what panel_fuse_check asks the occupancy of is what
 // panel_reduce_upd launches
 using PanelFusedFn = void (*)(PanelParams, int, int);
-PanelFusedFn panel_fused_fn(int U, bool masked) {
+PanelFusedFn panel_fused_fn(int U, bool masked, bool icpt) {
     return dispatch<1, 2, 4>(U, [&](auto u) -> PanelFusedFn {
+        if (icpt) return &k_panel_reduce_upd<decltype(u)::value, true, true>;
         return masked ? &k_panel_reduce_upd<decltype(u)::value, true> : &k_panel_reduce_upd<decltype(u)::value, false>;
     });
 }
 int panel_reduce_upd(bpgl_panel* c, int cflag) {
     int G = 0, U = 0;
     (void)panel_fused_geo(c, &G, &U);
-    hipLaunchKernelGGL(panel_fused_fn(U, c->masked), dim3((unsigned)(c->k * G)), dim3(kThreads), 0, c->stream, c->p,
+    hipLaunchKernelGGL(panel_fused_fn(U, c->masked, c->icpt), dim3((unsigned)(c->k * G)), dim3(kThreads), 0, c->stream, c->p,
                        cflag, G);
     LAUNCH_CHECK("k_panel_reduce_upd");
     return 0;
 }
 // the fused reduce + update needs its k x G blocks resident together: on the CUs the stream may use
 // (a CU-masked stream from bpgl_stream_create gets fewer), else the two-kernel form runs.  The
-// occupancy is that of the variant that will run (masked or not), so bpgl_panel_set_row_mask repeats it.
+// occupancy is that of the variant that will run (masked or not, with the intercept or not), so
+// bpgl_panel_set_row_mask and bpgl_panel_set_intercept repeat it.
 void panel_fuse_check(bpgl_panel* c) {
     int G = 0, U = 0, nb = 0;
     c->fuse_ok = 0;
     c->fuse_cus = 0;
     if (!panel_fused_geo(c, &G, &U)) return;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)panel_fused_fn(U, c->masked), kThreads, 0) !=
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)panel_fused_fn(U, c->masked, c->icpt), kThreads, 0) !=
         hipSuccess) {
         (void)hipGetLastError();   // the query's own error only
         return;
@@ -230,7 +251,8 @@ void panel_fuse_check(bpgl_panel* c) {
 // mode 0 (bpgl_panel_mm) is always the unmasked fold
 int panel_reduce(bpgl_panel* c, double* out, int mode) {
     const dim3 grid((unsigned)(c->k * cdiv(c->m, kLspRows)));
-    if (mode && c->masked) hipLaunchKernelGGL(k_panel_reduce<true>, grid, dim3(kThreads), 0, c->stream, c->p, out, mode);
+    if (mode && c->icpt) hipLaunchKernelGGL((k_panel_reduce<true, true>), grid, dim3(kThreads), 0, c->stream, c->p, out, mode);
+    else if (mode && c->masked) hipLaunchKernelGGL(k_panel_reduce<true>, grid, dim3(kThreads), 0, c->stream, c->p, out, mode);
     else hipLaunchKernelGGL(k_panel_reduce<false>, grid, dim3(kThreads), 0, c->stream, c->p, out, mode);
     LAUNCH_CHECK("k_panel_reduce");
     return 0;
@@ -255,7 +277,8 @@ int panel_iteration(bpgl_panel* c, int64_t it, bool exact = false, bool split_r 
     return c->tm.timed(4, it, [&] {
         if (c->nblock == 1 && c->defer_x) {   // R only; x += gamma D' rides on the next pass-1 epilogue (or the flush)
             const dim3 ug((unsigned)std::min<int64_t>(cdiv((int64_t)c->k * c->m / 4, kThreads), 8192));
-            hipLaunchKernelGGL(k_panel_update1, ug, dim3(kThreads), 0, c->stream, c->p, cflag);
+            if (c->icpt) hipLaunchKernelGGL(k_panel_update1<true>, ug, dim3(kThreads), 0, c->stream, c->p, cflag);
+            else hipLaunchKernelGGL(k_panel_update1<false>, ug, dim3(kThreads), 0, c->stream, c->p, cflag);
         } else {
             const int64_t n = (int64_t)c->k * c->w / 8 + (int64_t)c->k * c->m / 4;   // work units
             const dim3 ug((unsigned)std::min<int64_t>(cdiv(n, kThreads), 8192));
@@ -302,10 +325,14 @@ PanelGapArgs pgap_args(const bpgl_panel* c) {
     a.W = c->masked ? c->p.W : nullptr;
     a.Bh = c->at<double>(c->L.Bh);
     a.hpart = c->at<double>(c->L.ghold);
+    a.ipart = c->at<double>(c->L.gipart);
+    a.icp = c->at<double>(c->L.gicp);
+    a.nw = c->p.nw;
+    a.bmean = c->at<double>(c->L.bmean);
     return a;
 }
-// bpgl_panel_reset_x0: R = A X - B (w o (A X - B) with a row mask) from the stored X through the
-// certificate's product 1, and with nblock > 1 also Ax[b] = A_b x_b
+// bpgl_panel_reset_x0: R = A X - B (w o (A X - B) with a row mask, P_w(A X - B) with the intercept) from the
+// stored X through the certificate's product 1, and with nblock > 1 also Ax[b] = A_b x_b
 int panel_warm_residual(bpgl_panel* c) {
     PanelGapArgs a = pgap_args(c);
     if (c->nblock == 1) {   // the certificate's own chunking and fold, written to the solver's R
@@ -326,6 +353,34 @@ int panel_warm_residual(bpgl_panel* c) {
     if (c->masked) hipLaunchKernelGGL(k_pgap_fold_ax<true>, fgrid, blk, 0, c->stream, a, spb, c->p.Ax, c->p.R);
     else hipLaunchKernelGGL(k_pgap_fold_ax<false>, fgrid, blk, 0, c->stream, a, spb, c->p.Ax, c->p.R);
     LAUNCH_CHECK("k_pgap_fold_ax");
+    return 0;
+}
+
+// the mask in effect: the caller's, else (the intercept on) all ones, else none; with the intercept the
+// in-row counts too.  Then the fused form's occupancy check for the variant that will run.
+int panel_install_mask(bpgl_panel* c) {
+    unsigned char* W = c->at<unsigned char>(c->L.W);
+    if (c->icpt && !c->user_mask) HIP_TRY(hipMemsetAsync(W, 1, (int64_t)c->k * c->m, c->stream));
+    c->masked = c->user_mask || c->icpt;
+    c->p.W = c->masked ? W : nullptr;
+    if (c->icpt) {
+        hipLaunchKernelGGL(k_panel_count_rows, dim3((unsigned)c->k), dim3(kThreads), 0, c->stream, W, (long long)c->m,
+                           c->at<double>(c->L.nw));
+        LAUNCH_CHECK("k_panel_count_rows");
+    }
+    c->solver = false;   // B is stored masked and the graphs bake the kernel variant in: a reset must follow
+    drop_graphs(c);
+    panel_fuse_check(c);   // the occupancy of the variant that will run
+    return 0;
+}
+int panel_run_diag(bpgl_panel* c) {
+    const dim3 grid((unsigned)cdiv(c->n, 512));
+    if (c->icpt) hipLaunchKernelGGL(k_panel_diag_centred, grid, dim3(kThreads), 0, c->stream, c->p,
+                                    const_cast<double*>(c->p.diag), const_cast<double*>(c->p.rec));
+    else hipLaunchKernelGGL(k_panel_diag, grid, dim3(kThreads), 0, c->stream, c->p,
+                            const_cast<double*>(c->p.diag), const_cast<double*>(c->p.rec));
+    LAUNCH_CHECK("k_panel_diag");
+    c->have_diag = true;
     return 0;
 }
 
@@ -440,6 +495,9 @@ int bpgl_panel_bind(bpgl_panel* c, const void* A, int64_t lda, void* scratch, in
     p.lsdone = c->at<unsigned long long>(L.lsdone);
     p.At = c->at<__bf16>(L.At);
     p.A1t = c->at<__bf16>(L.A1t);
+    p.lss = c->at<double>(L.lss);
+    p.cshift = c->at<double>(L.cshift);
+    p.nw = c->at<double>(L.nw);
     HIP_TRY(hipSetDevice(c->device));
     // Cleared here: every region up to the tiled copies -- the state, counters and partials, the operand
     // images, X, Ax, B, R, diag / rec and the carried gradient's G, operand and E -- so that nothing reads
@@ -447,7 +505,8 @@ int bpgl_panel_bind(bpgl_panel* c, const void* A, int64_t lda, void* scratch, in
     // cleared, because each is written in full before it is read: At / A1t (the tile kernels below), the
     // certificate's buffers gpart, gparts, gcounts, gres and ghold (every bpgl_panel_gap writes them first),
     // W (bpgl_panel_set_row_mask, and p.W is null until then) and Bh (k_panel_mask_b at a masked reset; the
-    // certificate reads it only under a mask).
+    // certificate reads it only under a mask); the intercept's pieces (nw: bpgl_panel_set_intercept; bmean: the
+    // reset; lss and cshift: every iteration's line search before its update; gipart and gicp: every certificate).
     HIP_TRY(hipMemsetAsync(c->scratch, 0, L.At, c->stream));
     hipLaunchKernelGGL((k_panel_tile<256, 64, true>), dim3((unsigned)((c->m / 256) * (c->n / 64))), dim3(256), 0,
                        c->stream, p.A, p.lda, c->n, c->at<__bf16>(L.At));
@@ -455,7 +514,7 @@ int bpgl_panel_bind(bpgl_panel* c, const void* A, int64_t lda, void* scratch, in
     hipLaunchKernelGGL((k_panel_tile<64, 256, false>), dim3((unsigned)((c->m / 64) * (c->n / 256))), dim3(256), 0,
                        c->stream, p.A, p.lda, c->n, c->at<__bf16>(L.A1t));
     LAUNCH_CHECK("k_panel_tile");
-    c->masked = false;   // p.W is null again
+    c->masked = c->user_mask = c->icpt = c->icpt_valid = false;   // p.W is null again
     panel_fuse_check(c);
     c->bound = true;
     c->have_diag = false;
@@ -468,11 +527,8 @@ int bpgl_panel_diag(bpgl_panel* c, double* out) {
     int rc;
     if ((rc = panel_ready(c))) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    hipLaunchKernelGGL(k_panel_diag, dim3((unsigned)cdiv(c->n, 512)), dim3(kThreads), 0, c->stream, c->p,
-                       const_cast<double*>(c->p.diag), const_cast<double*>(c->p.rec));
-    LAUNCH_CHECK("k_panel_diag");
+    if ((rc = panel_run_diag(c))) return rc;   // the diag in effect: the centred one with the intercept on
     if (out) HIP_TRY(hipMemcpyAsync(out, c->p.diag, 8 * c->n, hipMemcpyDeviceToDevice, c->stream));
-    c->have_diag = true;
     return 0;
 }
 
@@ -511,10 +567,19 @@ int bpgl_panel_reset_x0(bpgl_panel* c, const double* B, const double* mu, const 
     if (!c->have_diag) return fail(BPGL_E_STATE, "bpgl_panel_diag must run before the solver");
     if (!B || !mu) return fail(BPGL_E_ARG, "B and mu must be non-null");
     if (((uintptr_t)X0) % 16) return fail(BPGL_E_ARG, "X0 must be 16-byte aligned");
+    if (c->icpt && c->nblock > 1)
+        return fail(BPGL_E_STATE, "the intercept needs one feature block (nblock is %d)", c->nblock);
+    if (c->icpt && !c->defer_x)
+        return fail(BPGL_E_STATE, "the intercept needs the deferred x update (the tuning key defer_x is 0)");
     HIP_TRY(hipSetDevice(c->device));
     PanelParams& p = c->p;
     const int64_t km = (int64_t)c->k * c->m;
-    if (c->masked) {   // the stored B is w o B (so R0 = -w o B and A x - B stays masked); (1 - w) o B for the score
+    c->icpt_valid = false;
+    if (c->icpt) {   // the stored B is P_w B (so R0 = -P_w B), its in-row mean kept for the certificate; (1 - w) o B as below
+        hipLaunchKernelGGL(k_panel_centre_b, dim3((unsigned)c->k), dim3(kThreads), 0, c->stream, B, p.W, (long long)c->m,
+                           p.nw, const_cast<double*>(p.B), c->at<double>(c->L.Bh), c->at<double>(c->L.bmean));
+        LAUNCH_CHECK("k_panel_centre_b");
+    } else if (c->masked) {   // the stored B is w o B (so R0 = -w o B and A x - B stays masked); (1 - w) o B for the score
         hipLaunchKernelGGL(k_panel_mask_b, dim3((unsigned)std::min<int64_t>(cdiv(km, kThreads), 2048)), dim3(kThreads),
                            0, c->stream, B, p.W, (long long)km, const_cast<double*>(p.B), c->at<double>(c->L.Bh));
         LAUNCH_CHECK("k_panel_mask_b");
@@ -707,11 +772,30 @@ int bpgl_panel_set_row_mask(bpgl_panel* c, const uint8_t* mask) {
     HIP_TRY(hipSetDevice(c->device));
     unsigned char* W = c->at<unsigned char>(c->L.W);
     if (mask) HIP_TRY(hipMemcpyAsync(W, mask, (int64_t)c->k * c->m, hipMemcpyDeviceToDevice, c->stream));
-    c->masked = mask != nullptr;
-    c->p.W = mask ? W : nullptr;
-    c->solver = false;   // B is stored masked and the graphs bake the kernel variant in: a reset must follow
-    drop_graphs(c);
-    panel_fuse_check(c);   // the occupancy of the variant that will run
+    c->user_mask = mask != nullptr;
+    return panel_install_mask(c);   // with the intercept on: all ones when cleared, and the in-row counts again
+}
+
+int bpgl_panel_set_intercept(bpgl_panel* c, int on) {
+    int rc;
+    if ((rc = panel_ready(c))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    c->icpt = on != 0;
+    c->icpt_valid = false;
+    if ((rc = panel_install_mask(c))) return rc;
+    return panel_run_diag(c);   // centred norms and rec with the intercept, k_panel_diag's without
+}
+
+int bpgl_panel_intercept(bpgl_panel* c, double* out) {
+    int rc;
+    if ((rc = panel_ready(c))) return rc;
+    if (!out) return fail(BPGL_E_ARG, "out is null");
+    if (!c->icpt) {
+        std::fill(out, out + c->k, 0.0);
+        return 0;
+    }
+    if (!c->icpt_valid) return fail(BPGL_E_STATE, "no bpgl_panel_gap since the last reset");
+    std::copy(c->icpt_host.begin(), c->icpt_host.end(), out);
     return 0;
 }
 
@@ -764,7 +848,12 @@ int bpgl_panel_gap(bpgl_panel* c, double* G_all, double* R_fresh, uint8_t* keep,
         LAUNCH_CHECK("k_pgap_count");
     }
     HIP_TRY(hipMemcpyAsync(out, res, sizeof(double) * kPgRes * c->k, hipMemcpyDeviceToHost, c->stream));
+    if (c->icpt) {   // beta0 per RHS, for bpgl_panel_intercept
+        c->icpt_host.resize(c->k);
+        HIP_TRY(hipMemcpyAsync(c->icpt_host.data(), a.icp + c->k, 8 * (int64_t)c->k, hipMemcpyDeviceToHost, c->stream));
+    }
     HIP_TRY(hipStreamSynchronize(c->stream));
+    c->icpt_valid = c->icpt;
     for (int q = 0; q < 2; ++q) {
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, c->gap_ev[q], c->gap_ev[q + 1]));

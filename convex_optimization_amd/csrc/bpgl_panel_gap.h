@@ -26,6 +26,14 @@
 //                           multiple of 256) the held-out sum of (1 - w_ki)(a_i . x_k - b_ki)^2 from Bh
 //   k_pgap_holdout          one block per RHS: res[k][7] = those block sums added in block order
 // Product 2 and everything after it then describe the masked problem; the screen keeps the full diag.
+// With the intercept (bpgl_panel_set_intercept; B is then stored as P_w B with its
+// in-row mean in bmean, and a mask is always installed):
+//   k_pgap_fold<1, true, true>   Rf[k][i] = a_i . x_k - (in ? (P_w b)_ki : b_ki) at EVERY row -- the uncentred
+//                           e, shifted by bmean_k at the in-rows -- and per block the in-row sum of it
+//   k_pgap_icpt_mean        one block per RHS: those sums in block order -> c' = sum / n_w, beta0 = bmean - c'
+//   k_pgap_centre           Rf = in ? Rf - c' : 0, i.e. P_w(A x - b); the held-out (e - c)^2 = (a.x + beta0 - b)^2,
+//                           squared directly, to the per-block partials that k_pgap_holdout consumes
+// Product 2 and everything after it read the centred Rf: the certificate of the profiled problem.
 // Every reduction walks its dimension in a fixed order (within a chunk: 32-deep stages in index
 // order, 4 at a time through the MFMA; then the chunks; then wave_sum / wave_max, the waves, the
 // blocks in index order).  No floating-point atomics: two calls on the same state return the same
@@ -75,6 +83,11 @@ struct PanelGapArgs {
     const unsigned char* W;   // [k][m]
     const double* Bh;     // [k][m]           (1 - w) o B
     double* hpart;        // [k m / 256]      held-out partial of each fold block
+    // intercept (null / unread without it): the centring of product 1
+    double* ipart;        // [k m / 256]      in-row sum of each fold block
+    double* icp;          // [2][k]           c' = the in-row mean of what the fold left; beta0
+    const double* nw;     // [k]              rows in each RHS's objective
+    const double* bmean;  // [k]              the in-row mean of b that the stored P_w B had subtracted
 };
 
 // bf16 e of 8 in a 16-byte piece -> fp64 (exact)
@@ -188,9 +201,10 @@ __global__ __launch_bounds__(kThreads) void k_pgap_prod(PanelGapArgs a) {
 // one thread per (rhs, output): the chunks in index order; product 1 subtracts B and writes Rf[k][i],
 // product 2 writes G[blk][k][j].  MK (product 1 with a row mask; a.B holds w o B): Rf = 0 at the
 // held-out rows, whose squared errors against Bh go to one partial per block (lanes, waves in order)
-template <int PROD, bool MK = false>
+template <int PROD, bool MK = false, bool IC = false>
 __global__ __launch_bounds__(kThreads) void k_pgap_fold(PanelGapArgs a) {
     static_assert(!MK || PROD == 1, "the mask enters product 1 only");
+    static_assert(!IC || MK, "the intercept runs on the masked fold");
     const long long len = PROD == 1 ? a.m : a.n;
     const long long e = (long long)blockIdx.x * kThreads + threadIdx.x;
     if constexpr (MK) {
@@ -198,6 +212,17 @@ __global__ __launch_bounds__(kThreads) void k_pgap_fold(PanelGapArgs a) {
         double v = a.part[e];
         for (int c = 1; c < a.spl; ++c) v += a.part[(long long)c * a.k * len + e];
         const bool in = a.W[e] != 0;
+        if constexpr (IC) {
+            const double ev = v - (in ? a.B[e] : a.Bh[e]);
+            a.Rf[e] = ev;
+            const double es = wave_sum(in ? ev : 0.0);
+            __shared__ double red[kWaves];
+            const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+            if (lane == 0) red[wave] = es;
+            __syncthreads();
+            if (threadIdx.x == 0) a.ipart[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+            return;
+        }
         a.Rf[e] = in ? v - a.B[e] : 0.0;
         const double h = in ? 0.0 : v - a.Bh[e];
         const double hh = wave_sum(h * h);
@@ -214,6 +239,47 @@ __global__ __launch_bounds__(kThreads) void k_pgap_fold(PanelGapArgs a) {
         if (PROD == 1) a.Rf[e] = v - a.B[e];
         else a.G[((o / a.w) * a.k + k) * a.w + o % a.w] = v;
     }
+}
+
+// intercept, one block per RHS: the nb fold blocks' in-row sums added in block order (loaded kThreads at a
+// time, thread 0 adding them in index order) -> icp[0][k] = c' = sum / n_w (0 for an all-zero mask column),
+// icp[1][k] = beta0 = bmean - c' = -mean_in(a_i . x - b_i)
+__global__ __launch_bounds__(kThreads) void k_pgap_icpt_mean(PanelGapArgs a, long long nb) {
+    const int k = blockIdx.x;
+    __shared__ double buf[kThreads];
+    double tot = 0.0;
+    for (long long q0 = 0; q0 < nb; q0 += kThreads) {
+        const long long q = q0 + threadIdx.x;
+        if (q < nb) buf[threadIdx.x] = a.ipart[(long long)k * nb + q];
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int i = 0; i < kThreads && q0 + i < nb; ++i) tot += buf[i];
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    const double n = a.nw[k];
+    const double c = n > 0.0 ? tot / n : 0.0;
+    a.icp[k] = c;
+    a.icp[a.k + k] = n > 0.0 ? a.bmean[k] - c : 0.0;
+}
+
+// intercept, one thread per (rhs, row) (k m is a multiple of kThreads and a block lies in one RHS, as in the
+// masked fold): Rf = e' - c' at the in-rows, 0 at the others; the held-out rows' e - c = e' - c' + bmean
+// squared directly (no expanded square) into the block's partial, lanes then waves in order
+__global__ __launch_bounds__(kThreads) void k_pgap_centre(PanelGapArgs a) {
+    const long long e = (long long)blockIdx.x * kThreads + threadIdx.x;
+    const long long k = e / a.m;
+    const double c = a.icp[k], bm = a.bmean[k];
+    const bool in = a.W[e] != 0;
+    const double ev = a.Rf[e];
+    a.Rf[e] = in ? ev - c : 0.0;
+    const double h = in ? 0.0 : (ev - c) + bm;
+    const double hh = wave_sum(h * h);
+    __shared__ double red[kWaves];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) red[wave] = hh;
+    __syncthreads();
+    if (threadIdx.x == 0) a.hpart[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
 }
 
 // bpgl_panel_reset_x0 with more than one feature block: product 1 ran with its

@@ -35,6 +35,9 @@ panel (K folds x J values of mu = K J columns on one bound A; DESIGN.md section 
 ``PanelLasso.solver_reset(x0=...)`` starts the panel at a given x and ``gather_columns`` compacts the
 bound A; ``lasso_path`` and ``lasso_cv`` use them, opt-in, to warm-start and to drop columns the
 gap-safe screen proves zero for every right-hand side.
+``PanelLasso.set_intercept`` gives every right-hand side an unpenalised intercept, centred over that
+right-hand side's own in-rows inside the fold, and ``lasso_path`` / ``lasso_cv`` take ``fit_intercept``
+(DESIGN.md section 13).
 
 All compute goes through libbpgl.so (bpgl_panel_* in include/bpgl.h).
 """
@@ -73,6 +76,8 @@ _PANEL_SIGS = {
     "bpgl_panel_set_row_mask": (ctypes.c_int, [_p, _p]),
     "bpgl_panel_reset_x0": (ctypes.c_int, [_p, _p, _p, _p, _p, _i64, ctypes.c_int]),
     "bpgl_panel_gather_columns": (ctypes.c_int, [_p, _p, _i64, _p, _i64]),
+    "bpgl_panel_set_intercept": (ctypes.c_int, [_p, ctypes.c_int]),
+    "bpgl_panel_intercept": (ctypes.c_int, [_p, ctypes.POINTER(ctypes.c_double)]),
 }
 N._SIGS.update(_PANEL_SIGS)
 
@@ -257,6 +262,18 @@ class PanelLasso:
                 self._mask = (t.to(self.device) != 0).to(torch.uint8).t().contiguous()   # [k][m]
             N.check(_lib().bpgl_panel_set_row_mask(self._ctx, N.ptr(self._mask)), "bpgl_panel_set_row_mask")
 
+    def set_intercept(self, on):
+        """An unpenalised intercept per right-hand side (bpgl_panel_set_intercept; one feature block):
+        every column minimises 1/2 ||w o (A x + beta0 - b)||^2 + mu ||x||_1 over x and beta0, beta0
+        profiled out over the column's in-rows (all rows without a row mask).  A ``solver_reset`` (with the
+        full B) must follow.  ``diag_ATA`` is then the centred column norms sum_i (a_ij - mean_j)^2,
+        ``residual_device`` the centred residual, and ``duality_gap`` certifies the profiled problems and
+        reports ``intercept``.  ``set_intercept(False)`` restores the plain solver bitwise."""
+        with self._on_stream():
+            N.check(_lib().bpgl_panel_set_intercept(self._ctx, int(bool(on))), "bpgl_panel_set_intercept")
+            N.check(_lib().bpgl_panel_diag(self._ctx, N.ptr(self._diag)), "bpgl_panel_diag")   # the diag in effect
+        self._intercept = bool(on)
+
     def solver_step(self, n_iter):
         with self._on_stream():
             N.check(_lib().bpgl_panel_step(self._ctx, int(n_iter)), "bpgl_panel_step")
@@ -317,7 +334,9 @@ class PanelLasso:
         tensors g (k, n) fp64 = A^T r, r (k, m) fp64 = A x - b recomputed from x, keep (k, n) bool
         (None when ``screen`` is false; n_keep is then n).  drift is max |solver residual - r| per RHS.
         Also holdout_sse (k,): with a row mask the sum of squared errors over each column's held-out
-        rows (everything else then describes the masked problem), zero without one.
+        rows (everything else then describes the masked problem), zero without one; and intercept (k,):
+        with ``set_intercept`` each column's beta0 = -mean over its in-rows of (A x - b) (everything else
+        then describes the profiled problem, holdout_sse includes beta0), zero without it.
         Read-only for the solve and bitwise repeatable.  The tensors are views of buffers the next call
         overwrites (g is a copy when there is more than one feature block)."""
         k, n, m = self.nrhs, self.MAT_WIDTH_ALL, self.MAT_HEIGHT
@@ -334,6 +353,9 @@ class PanelLasso:
         res = {key: out[:, i].copy() for i, key in enumerate(self.GAP_KEYS)}
         res["n_keep"] = res["n_keep"].astype(np.int64)
         res["holdout_sse"] = out[:, 7].copy()
+        b0 = (ctypes.c_double * k)()
+        N.check(_lib().bpgl_panel_intercept(self._ctx, b0), "bpgl_panel_intercept")
+        res["intercept"] = np.array(b0, dtype=np.float64)
         res["g"] = self._gap_g.permute(1, 0, 2).reshape(k, n)
         res["r"] = self._gap_r
         res["keep"] = self._gap_keep.view(torch.bool) if screen else None
@@ -404,13 +426,14 @@ def _check_shrink(shrink):
     return float(shrink)
 
 
-def _screened_loop(pl, B, mu, target, ITER_MAX, check_every, shrink, mask=None):
+def _screened_loop(pl, B, mu, target, ITER_MAX, check_every, shrink, mask=None, intercept=False):
     """``_check_loop`` on a freshly reset ``pl`` (reset with ``B``, ``mu``; ``mask``: the (m, k) row mask
     installed on it, or None) with gap-safe compaction, ``ClassLassoScreened``'s rule on a panel: after
     a check that did not stop the loop, the union over the panel's columns of the screen's keep goes
     through ``cpu_calculation.compaction_columns`` with q = Block * 256; when that leaves at most
     ``shrink`` times the active columns, they are gathered (``gather_columns``), a new ``PanelLasso`` of
-    the same Block and width is built over them, the mask installed there, and the solve continues
+    the same Block and width is built over them, the mask (and, with ``intercept``, the intercept, which
+    ``pl`` then has on too) installed there, and the solve continues
     from ``solver_reset(B, mu, x0=X[sel])``.  ``pl`` stays alive; an earlier narrow context is dropped.
 
     Returns dict(t, cert, first, reached, x (n, k), active, compactions [(t, n_active after)],
@@ -443,6 +466,8 @@ def _screened_loop(pl, B, mu, target, ITER_MAX, check_every, shrink, mask=None):
             sel_d = torch.from_numpy(sel).to(cur.device)
             x0 = cur.solver_x_device()[:, sel_d].clone()          # (k, n_new) fp32
             nxt = PanelLasso(cur.gather_columns(sel_d), pl.Block, nrhs=k, device=pl.device)
+            if intercept:
+                nxt.set_intercept(True)
             if mask is not None:
                 nxt.set_row_mask(mask)
             nxt.solver_reset(B, mu, x0=x0)
@@ -466,7 +491,7 @@ def _screened_loop(pl, B, mu, target, ITER_MAX, check_every, shrink, mask=None):
 
 
 def lasso_path(A, b, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_BOUND=1e-4, ITER_MAX=4096,
-               check_every=PATH_CHECK_EVERY, device=None, x0=None, shrink=0.0):
+               check_every=PATH_CHECK_EVERY, device=None, x0=None, shrink=0.0, fit_intercept=False):
     """A regularization path as ONE panel: min 1/2 ||A x - b||^2 + mu ||x||_1 for every mu of a grid,
     on the bf16-stored A, every column of the panel holding the same b.
 
@@ -490,11 +515,18 @@ def lasso_path(A, b, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_BOUND=1e-4
     the last certificate's primal, dual, gap, scale, gnorm_inf, n_keep, drift per mu (after a
     compaction: of the final x on the full A, n_keep = n); active (the original indices still active
     at the end, arange(n) without compaction), compactions (a list of (t, n_active after)) and
-    compact_seconds (gather, the new context, its reset and graph capture)."""
+    compact_seconds (gather, the new context, its reset and graph capture).
+
+    ``fit_intercept`` (``Block`` must be 1, ValueError otherwise): every mu solves
+    min over x, beta0 of 1/2 ||A x + beta0 - b||^2 + mu ||x||_1 (``PanelLasso.set_intercept``, also on
+    every narrower context of ``shrink``).  mu_max is then ||A^T (b - mean b)||_inf, the bound
+    GAP_BOUND * 1/2 ||b - mean b||^2, and ``intercept`` (len(mus),) is returned (zeros without it)."""
     from .cpu_calculation import mu_grid
     if int(check_every) <= 0:
         raise ValueError("check_every must be > 0")
     shrink = _check_shrink(shrink)
+    if fit_intercept and int(Block) != 1:
+        raise ValueError("fit_intercept needs Block = 1")
     if x0 is not None and mus is None:
         raise ValueError("x0 needs mus: the grid the columns of x0 belong to")
     b = np.asarray(b.detach().cpu() if isinstance(b, torch.Tensor) else b, dtype=np.float64).reshape(-1)
@@ -512,6 +544,8 @@ def lasso_path(A, b, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_BOUND=1e-4
         grid, n_given = pad_mus(mus)
         k = grid.size
     pl = PanelLasso(A, Block, nrhs=k, device=device)
+    if fit_intercept:
+        pl.set_intercept(True)
     B = np.repeat(b[:, None], k, axis=1)
     mu_max = None
     if grid is None:
@@ -523,20 +557,22 @@ def lasso_path(A, b, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_BOUND=1e-4
     else:
         pad = np.repeat(x0[:, [int(np.argmax(grid[:n_given]))]], k - n_given, axis=1)
         pl.solver_reset(B, grid, x0=np.concatenate([x0, pad], axis=1))
-    target = float(GAP_BOUND) * 0.5 * float(b @ b)
-    run = _screened_loop(pl, B, grid, target, ITER_MAX, check_every, shrink)
+    bc = b - b.mean() if fit_intercept else b
+    target = float(GAP_BOUND) * 0.5 * float(bc @ bc)
+    run = _screened_loop(pl, B, grid, target, ITER_MAX, check_every, shrink, intercept=bool(fit_intercept))
     cert = run["cert"]
     out = dict(x=run["x"][:, :n_given], mus=grid[:n_given].copy(), mu_max=mu_max, iters=run["t"],
                reached=run["reached"][:n_given], first_reached=run["first"][:n_given])
     for key in PanelLasso.GAP_KEYS:
         out[key] = cert[key][:n_given]
+    out["intercept"] = cert["intercept"][:n_given]
     out.update(active=run["active"], compactions=run["compactions"], compact_seconds=run["compact_seconds"])
     return out
 
 
 def lasso_cv(A, b, n_folds=8, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_BOUND=1e-4, ITER_MAX=4096,
              check_every=PATH_CHECK_EVERY, seed=0, masks=None, refit=True, return_x=False, device=None,
-             shrink=0.0, warm_refit=False):
+             shrink=0.0, warm_refit=False, fit_intercept=False):
     """K-fold cross-validation over a grid of mu as ONE panel on one bound A: column c = f * n_mus + j
     solves fold f (the rows of ``masks[f]``) at ``mus[j]``, min 1/2 ||w_f o (A x - b)||^2 + mu_j ||x||_1,
     through ``PanelLasso.set_row_mask``.  n_folds * n_mus <= 128 and n_folds >= 2 (ValueError
@@ -563,11 +599,21 @@ def lasso_cv(A, b, n_folds=8, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_B
     fold solve and in the refit, the mask installed on every narrower context; mse, gap and n_keep then
     come from the certificate of the final x on the full A.  Also returned: active, compactions,
     compact_seconds of the fold solve (and refit_compactions).  ``warm_refit``: the refit starts each mu
-    from the mean over folds of that mu's fold solutions instead of from 0."""
+    from the mean over folds of that mu's fold solutions instead of from 0.
+
+    ``fit_intercept`` (``Block`` must be 1, ValueError otherwise): every column also
+    fits an unpenalised intercept, centred over the training rows of ITS fold inside the panel
+    (``PanelLasso.set_intercept``); the refit and every narrower context of ``shrink`` get it too.  mu_max
+    is then ||A^T (b - mean b)||_inf, the bound GAP_BOUND * 1/2 ||P_w b||^2 (b centred over the fold's
+    training rows), mse scores a_i . x + beta0 against b_i, and ``intercept_folds`` (n_folds, n_mus) and,
+    with ``refit``, ``intercept`` (n_mus,) are returned."""
     from .cpu_calculation import kfold_masks, mu_grid
     if int(check_every) <= 0:
         raise ValueError("check_every must be > 0")
     shrink = _check_shrink(shrink)
+    if fit_intercept and int(Block) != 1:
+        raise ValueError("fit_intercept needs Block = 1")
+    fit_intercept = bool(fit_intercept)
     b = np.asarray(b.detach().cpu() if isinstance(b, torch.Tensor) else b, dtype=np.float64).reshape(-1)
     m = b.size
     if masks is not None:
@@ -589,6 +635,8 @@ def lasso_cv(A, b, n_folds=8, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_B
         masks = kfold_masks(m, n_folds, seed)
     k = next(v for v in PANEL_NRHS if v >= ncol)
     pl = PanelLasso(A, Block, nrhs=k, device=device)
+    if fit_intercept:
+        pl.set_intercept(True)
     B = np.repeat(b[:, None], k, axis=1)
     if mus is None:
         pl.solver_reset(B, 1.0)
@@ -597,9 +645,12 @@ def lasso_cv(A, b, n_folds=8, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_B
     fold, jmu = cols // n_mus, cols % n_mus
     pl.set_row_mask(masks[fold].T)
     pl.solver_reset(B, mus[jmu])
-    bb = np.array([float((masks[f] * b) @ (masks[f] * b)) for f in range(n_folds)])
+    def centred(wf, v):   # w o v, or P_w v with the intercept
+        return wf * (v - (wf @ v) / wf.sum()) if fit_intercept else wf * v
+    bb = np.array([float(centred(masks[f].astype(np.float64), b) @ centred(masks[f].astype(np.float64), b))
+                   for f in range(n_folds)])
     run = _screened_loop(pl, B, mus[jmu], float(GAP_BOUND) * 0.5 * bb[fold], ITER_MAX, check_every, shrink,
-                         mask=masks[fold].T)
+                         mask=masks[fold].T, intercept=fit_intercept)
     t, cert = run["t"], run["cert"]
     shape = (n_folds, n_mus)
     count = (masks == 0).sum(axis=1).astype(np.float64)
@@ -613,6 +664,8 @@ def lasso_cv(A, b, n_folds=8, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_B
                reached=run["reached"][:ncol].reshape(shape),
                gap=cert["gap"][:ncol].reshape(shape), n_keep=cert["n_keep"][:ncol].reshape(shape), masks=masks,
                active=run["active"], compactions=run["compactions"], compact_seconds=run["compact_seconds"])
+    if fit_intercept:
+        out["intercept_folds"] = cert["intercept"][:ncol].reshape(shape)
     if return_x:
         out["x_folds"] = run["x"][:, :ncol].reshape(-1, n_folds, n_mus)
     if refit:
@@ -624,7 +677,11 @@ def lasso_cv(A, b, n_folds=8, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_B
             pl.solver_reset(B, grid, x0=xm)
         else:
             pl.solver_reset(B, grid)
-        rrun = _screened_loop(pl, B, grid, float(GAP_BOUND) * 0.5 * float(b @ b), ITER_MAX, check_every, shrink)
+        bc = b - b.mean() if fit_intercept else b
+        rrun = _screened_loop(pl, B, grid, float(GAP_BOUND) * 0.5 * float(bc @ bc), ITER_MAX, check_every, shrink,
+                              intercept=fit_intercept)
         out.update(x=rrun["x"][:, :n_mus], refit_gap=rrun["cert"]["gap"][:n_mus], refit_iters=rrun["t"],
                    refit_compactions=rrun["compactions"])
+        if fit_intercept:
+            out["intercept"] = rrun["cert"]["intercept"][:n_mus]
     return out

@@ -84,7 +84,13 @@ const char* bpgl_last_error(void);
  *                certificate's fp64 product 1) and bpgl_panel_gather_columns (a column-compacted copy
  *                of the bound A); bpgl_panel_reset is bpgl_panel_reset_x0 with X0 = NULL, bit for bit
  *                as before.  bpgl_panel_scratch_bytes grows only for nblock > 1 where the product's
- *                block-aligned chunks need more than the certificate's partials (see below). */
+ *                block-aligned chunks need more than the certificate's partials (see below).
+ *   307 (0.3.7): + bpgl_panel_set_intercept and bpgl_panel_intercept (an unpenalised intercept per
+ *                right-hand side, profiled out over that right-hand side's in-rows, so K folds with K
+ *                different centrings still share one bound A).  Opt-in: with it off
+ *                every kernel that existed is unchanged.  bpgl_panel_scratch_bytes grows by the pieces
+ *                laid out after everything that existed (one more line-search partial per 1024-row group,
+ *                a few nrhs-long vectors, the certificate's in-row partials). */
 int bpgl_version(void);
 
 /*
@@ -493,6 +499,41 @@ int bpgl_panel_gap(bpgl_panel* ctx, double* G_all, double* R_fresh, uint8_t* kee
  * fused update's occupancy check is repeated for the variant that will run.
  */
 int bpgl_panel_set_row_mask(bpgl_panel* ctx, const uint8_t* mask);
+/*
+ * Intercept (since ABI 307): with `on` nonzero every right-hand side solves
+ *   min over x, beta0 of 1/2 || w_k o (A x + beta0 1 - b_k) ||^2 + mu_k ||x||_1
+ * with beta0 unpenalised.  beta0 is profiled out: the objective is 1/2 ||P_w (A x - b)||^2 + mu ||x||_1 with
+ * P_w v = w o (v - (w . v) / n_w) (centre over the in-rows, n_w = sum w), and the solver carries the
+ * centred residual R = P_w (A x - b).  Pass 1 and pass 2 are the unchanged kernels; the split-K fold
+ * publishes one more partial per 1024-row group (sum s), the line search uses c = sum s / n_w
+ * (|P_w s|^2 = s.s - c sum s; gamma = 0 when that is <= 0) and publishes c beside gamma, and the update
+ * adds gamma (s - c) at the in-rows and leaves the held-out rows exactly 0.
+ * The call installs what the variant needs: without a caller's mask an all-ones mask of the library's own
+ * (bpgl_panel_set_row_mask(NULL) then re-installs it; a caller's mask is kept and its rows recounted);
+ * the in-row counts n_w; and the diag that fits -- on: d_j = sum_i (a_ij - mean_j)^2 over ALL rows (two
+ * fixed-order fp64 walks: means, then squared deviations), which dominates every fold's curvature
+ * ||P_w a_j||^2, with 1 / d_j = 0 stored where d_j = 0 (a constant column: its x stays 0, the intercept
+ * absorbs it); off: bpgl_panel_diag's values, bitwise.  bpgl_panel_diag afterwards returns the diag in effect.
+ * It invalidates the solver and drops the graphs exactly as bpgl_panel_set_row_mask does (bpgl_panel_step /
+ * bpgl_panel_gap return BPGL_E_STATE until the next reset) and repeats the fused update's occupancy check.
+ * The reset still takes the full B; the library stores P_w B (so R0 = -P_w B) and (1 - w) o B.
+ * Limits: the intercept is built for one feature block with the deferred x update only.  With it on,
+ * bpgl_panel_reset / bpgl_panel_reset_x0 return BPGL_E_STATE for nblock > 1 and for the tuning key
+ * defer_x = 0.  An all-zero mask column (n_w = 0) takes no steps and reports zeros.
+ * bpgl_panel_gap then certifies the profiled problems: R_fresh = P_w (A x - b) (exactly 0 at held-out rows;
+ * it sums to zero over the in-rows, which is the intercept's dual constraint), G, primal, dual, gap, scale,
+ * ||g||_inf and drift from it, the screen with the centred diag, and out[8 k + 7] = the held-out sum of
+ * (a_i . x_k + beta0_k - b_ki)^2, each difference squared directly.  bpgl_panel_reset_x0 starts at
+ * R = P_w (A X0 - B) through the same kernels, so a certificate right after it reports drift 0.
+ * Legal any time after bpgl_panel_bind (BPGL_E_STATE before it; BPGL_E_ARG on a null context).
+ */
+int bpgl_panel_set_intercept(bpgl_panel* ctx, int on);
+/*
+ * beta0_k = -mean over the in-rows of (a_i . x_k - b_ki) at the x of the last bpgl_panel_gap (since ABI
+ * 307).  out: host, nrhs doubles.  BPGL_E_STATE if no bpgl_panel_gap has run since the last reset; zeros
+ * (and no such requirement) with the intercept off.
+ */
+int bpgl_panel_intercept(bpgl_panel* ctx, double* out);
 /*
  * Warm start (since ABI 306): bpgl_panel_reset at a given iterate.
  * X0: device fp32 [nblock][nrhs][w] (the layout of bpgl_panel_x), 16-byte aligned, caller-owned.
