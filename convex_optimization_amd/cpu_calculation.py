@@ -22,7 +22,8 @@ of a regularization path; ``kfold_masks``, ``masked_panel_iterate`` and ``masked
 restatement of the panel's row-masked problems (K-fold cross-validation, DESIGN.md section 11);
 ``compaction_columns``, the columns a screened panel keeps when it is compacted (DESIGN.md section 12);
 ``centred_diag``, ``intercept_panel_iterate`` and ``intercept_duality_gap``, the restatement of the
-panel's intercept.
+panel's intercept; ``positive_panel_iterate`` and ``positive_duality_gap``, the
+restatement of the panel's non-negative lasso (x >= 0).
 """
 import numpy as np
 
@@ -293,6 +294,95 @@ def intercept_duality_gap(A, b, w, x, mu, diag=None):
     score = scale * np.abs(g) + np.sqrt(dg) * np.sqrt(2.0 * np.maximum(gap, 0.0))
     return dict(primal=primal, dual=dual, gap=gap, scale=scale, gnorm_inf=gn, holdout_sse=float(h @ h),
                 intercept=-c if nw > 0 else 0.0, score=score, keep=~(score < mu), g=g, r=r)
+
+
+# ---------------------------------------------------------------------------
+# Non-negative lasso: min 1/2 || w o (A x - b) ||^2 + mu sum_j x_j subject to x >= 0,
+# with or without the intercept's profiling.  The host restatement of bpgl_panel_set_positive's solver and
+# certificate.
+# ---------------------------------------------------------------------------
+def positive_panel_iterate(A, b, w, mu, Block, iters, diag=None, x0=None, intercept=False):
+    """``iters`` block updates (cyclic over ``Block`` feature blocks; ``intercept`` needs Block = 1) of the
+    panel's iteration on the non-negative problem of one right-hand side, in fp64: R = w o (A x - b)
+    (P_w (A x - b) with ``intercept``), G = A_m^T R, the one-sided prox x^ = max(0, S(d x - G, mu) / d)
+    (x^ = 0 where d = 0), D = x^ - x, S = w o (A_m D), the exact line search along D (curvature |P_w S|^2
+    with ``intercept``) and x += gamma D.  ``w`` None: all rows.  ``diag``: default the full column norms
+    (``centred_diag(A)`` with ``intercept``).  ``x0`` is projected to max(x0, 0).  Returns dict(x, r[,
+    intercept]); x >= 0 at every iteration."""
+    A = np.asarray(A, dtype=np.float64)
+    m, n = A.shape
+    Block = int(Block)
+    if intercept and Block != 1:
+        raise ValueError("intercept needs Block = 1")
+    wd = n // Block
+    b = np.asarray(b, dtype=np.float64).reshape(-1)
+    w = np.ones(m) if w is None else (np.asarray(w).reshape(-1) != 0).astype(np.float64)
+    nw = float(w.sum())
+    mu = float(mu)
+    if diag is None:
+        dg = centred_diag(A) if intercept else np.square(A).sum(axis=0)
+    else:
+        dg = np.asarray(diag, dtype=np.float64).reshape(-1)
+    with np.errstate(divide="ignore"):
+        rec = np.where(dg > 0, 1.0 / np.where(dg > 0, dg, 1.0), 0.0).reshape(Block, wd)
+    dg = dg.reshape(Block, wd)
+    x = np.maximum(np.zeros(n) if x0 is None else np.array(x0, dtype=np.float64).reshape(-1), 0.0).reshape(Block, wd)
+    proj = (lambda v: _centre(w, v)) if intercept else (lambda v: w * v)
+    R = proj(A @ x.reshape(-1) - b)
+    for t in range(int(iters)):
+        mb = t % Block
+        Am = A[:, mb * wd:(mb + 1) * wd]
+        g = Am.T @ R
+        rx = dg[mb] * x[mb] - g
+        Bx = np.maximum(rec[mb] * (np.sign(rx) * np.maximum(np.abs(rx) - mu, 0)), 0.0)
+        D = Bx - x[mb]
+        s = w * (Am @ D)
+        ps = proj(Am @ D)
+        r1 = R @ s + mu * D.sum()          # |x + D|_1 - |x|_1 on the feasible set, without the cancellation
+        r2 = ps @ ps
+        gamma = 0.0 if r2 <= 0 else float(np.clip(-r1 / r2, 0, 1))
+        x[mb] = x[mb] + gamma * D          # >= 0: D >= -x and gamma <= 1, each rounding monotone
+        R = R + gamma * ps
+    out = dict(x=x.reshape(-1), r=R)
+    if intercept:
+        e = A @ out["x"] - b
+        out["intercept"] = -(float(w @ e) / nw) if nw > 0 else 0.0
+    return out
+
+
+def positive_duality_gap(A, b, w, x, mu, diag=None, intercept=False):
+    """The certificate of the non-negative problem at a feasible x: r = w o (A x - b) (P_w (A x - b) with
+    ``intercept``), g = A^T r.  The dual constraint is one-sided, -a_j . theta <= mu, so gnorm_inf is
+    max_j (-g_j)+, scale = min(1, mu / that) (1 when it is 0) makes scale r dual feasible, and primal =
+    1/2 |r|^2 + mu sum |x|, dual = -1/2 scale^2 |r|^2 - scale r.b, gap = primal - dual >= P(x) - P* as in
+    ``masked_duality_gap``.  The gap-safe score is scale (-g_j) + sqrt(d_j) sqrt(2 max(gap, 0)), keep =
+    not (score < mu): a column that is not kept is 0 at every optimum.  ``w`` None: all rows; ``diag``: default
+    the full column norms (``centred_diag(A)`` with ``intercept``).  Also holdout_sse and intercept as in
+    ``masked_duality_gap`` / ``intercept_duality_gap``."""
+    A = np.asarray(A, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64).reshape(-1)
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    w = np.ones(A.shape[0]) if w is None else (np.asarray(w).reshape(-1) != 0).astype(np.float64)
+    nw = float(w.sum())
+    mu = float(mu)
+    e = A @ x - b
+    c = (float(w @ e) / nw if nw > 0 else 0.0) if intercept else 0.0
+    r = w * (e - c)
+    g = A.T @ r
+    rr = float(r @ r)
+    primal = 0.5 * rr + mu * float(np.abs(x).sum())
+    gn = float(np.max(np.where(g > 0, 0.0, -g)))       # NaN propagates
+    scale = min(1.0, mu / gn) if gn > 0.0 else 1.0
+    dual = -0.5 * scale * scale * rr - scale * float(r @ b)
+    gap = primal - dual
+    h = (1.0 - w) * (e - c)
+    if diag is None:
+        dg = centred_diag(A) if intercept else np.square(A).sum(axis=0)
+    else:
+        dg = np.asarray(diag, dtype=np.float64).reshape(-1)
+    score = scale * (-g) + np.sqrt(dg) * np.sqrt(2.0 * np.maximum(gap, 0.0))
+    return dict(primal=primal, dual=dual, gap=gap, scale=scale, gnorm_inf=gn, holdout_sse=float(h @ h),
+                intercept=-c if (intercept and nw > 0) else 0.0, score=score, keep=~(score < mu), g=g, r=r)
 
 
 # ---------------------------------------------------------------------------

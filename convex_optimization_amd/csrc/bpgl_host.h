@@ -1,5 +1,6 @@
 // Host-side helpers shared by the two C-ABI translation units of libbpgl.so
-// (bpgl.hip: single right-hand side; bpgl_panel_abi.hip: k right-hand sides).
+// (bpgl.hip: single right-hand side; bpgl_panel_abi.hip: k right-hand sides) and by bpgl_panel_pos.hip,
+// which holds kernel variants only.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -538,9 +538,20 @@ __device__ __forceinline__ void panel_x_update8(const PanelParams& p, float* X, 
     *reinterpret_cast<float4*>(xp + 4) = make_float4(xs[4], xs[5], xs[6], xs[7]);
 }
 
+// the bf16 neighbour of h towards +inf (for a negative h: towards zero; -min -> -0)
+__device__ __forceinline__ __bf16 bf16_next_up(__bf16 h) {
+    const unsigned short b = __builtin_bit_cast(unsigned short, h);
+    return __builtin_bit_cast(__bf16, (unsigned short)((b & 0x8000u) ? b - 1 : b + 1));
+}
 // one (RHS tile, column group) step of the shrink epilogue: the lane's 4 columns of one RHS -- g from
 // the product (+ the carried G), the prox step, D' in DS bf16 pieces, the norm / error partials
-template <int DS, int GM>
+// POS (bpgl_panel_set_positive): the problem is min ... subject to x >= 0.  The prox is
+// the one-sided threshold max(0, S(d x - g, mu) / d); the image D' is made feasible -- x + D' >= 0 in the
+// fp64 arithmetic of `dprime`, which is what panel_apply_x adds -- by moving a nearest image that overshoots
+// -x one bf16 step up (the image itself with DS = 1, its lo piece with DS = 2; one step suffices: the
+// nearest image r of v >= -x has its upper neighbour r' >= v); err is the constrained prox residual
+// |x - max(0, x - g - mu)|.  x >= 0 on entry (the reset projects X0), so every stored iterate stays >= 0.
+template <int DS, int GM, bool POS = false>
 __device__ __forceinline__ void panel_shrink4(const f32x4& acc, const float (&xs)[4], float (&gs)[4],
                                               const double (&dgv)[4], const double (&rcv)[4], double mu,
                                               __bf16 (&dh)[4], __bf16 (&dl)[4], double& sbx, double& sx,
@@ -551,18 +562,37 @@ __device__ __forceinline__ void panel_shrink4(const f32x4& acc, const float (&xs
         if constexpr (GM == 2) g = (double)gs[r] + g;
         if constexpr (GM != 0) gs[r] = (float)g;
         const double x = (double)xs[r];
-        const double bx = rcv[r] * soft_thr(dgv[r] * x - g, mu);
+        double bx = rcv[r] * soft_thr(dgv[r] * x - g, mu);
+        if constexpr (POS) bx = bx < 0.0 ? 0.0 : bx;   // (a NaN stays a NaN)
         double dprime;
         if constexpr (DS == 2) {
             split_bf16(bx - x, dh[r], dl[r]);
             dprime = (double)(float)dh[r] + (double)(float)dl[r];
+            if constexpr (POS) {
+                if (x + dprime < 0.0) {
+                    dl[r] = bf16_next_up(dl[r]);
+                    dprime = (double)(float)dh[r] + (double)(float)dl[r];
+                }
+            }
         } else {
             dh[r] = to_bf16((float)(bx - x));
             dprime = (double)(float)dh[r];
+            if constexpr (POS) {
+                if (x + dprime < 0.0) {
+                    dh[r] = bf16_next_up(dh[r]);
+                    dprime = (double)(float)dh[r];
+                }
+            }
         }
         sbx += fabs(x + dprime);
         sx += fabs(x);
-        const double e = fabs(g - proj(g - x, -mu, mu));
+        double e;
+        if constexpr (POS) {
+            const double px = x - g - mu;
+            e = fabs(x - (px > 0.0 ? px : 0.0));
+        } else {
+            e = fabs(g - proj(g - x, -mu, mu));
+        }
         err = nan_max(err, e);
     }
 }
@@ -599,7 +629,7 @@ __device__ __forceinline__ void panel_norms_out(const PanelParams& p, const doub
 }
 
 // (BPGL_PANEL_DIAG's epilogue bits: see the macro.)
-template <int NTW, int EPI, int DS, int GM = 0, int NW = 0>
+template <int NTW, int EPI, int DS, int GM = 0, int NW = 0, bool POS = false>
 __device__ __forceinline__ void panel_pass1_epilogue(const PanelParams& p, int mb, long long c0, int wm, int wn,
                                                      int T, f32x4 (&acc)[4][NTW], char* smem,
                                                      double* __restrict__ Gout) {
@@ -724,7 +754,7 @@ __device__ __forceinline__ void panel_pass1_epilogue(const PanelParams& p, int m
                         put(p.X, ((long long)mb * p.k + rhs) * p.w + j, make_float4(xs[0], xs[1], xs[2], xs[3]));
                 }
                 __bf16 dh[4], dl[4];
-                panel_shrink4<DS, GM>(acc[mt][nt], xs, gs, dgv, rcv, mu, dh, dl, sbx, sx, err);
+                panel_shrink4<DS, GM, POS>(acc[mt][nt], xs, gs, dgv, rcv, mu, dh, dl, sbx, sx, err);
                 if constexpr (GM != 0)   // read again only next iteration, after all of A: non-temporal
                     __builtin_nontemporal_store(f32x4{gs[0], gs[1], gs[2], gs[3]},
                                                 reinterpret_cast<f32x4*>(p.Gc + (long long)rhs * p.w + j));
@@ -822,7 +852,7 @@ __device__ __forceinline__ void panel_pass1_epilogue(const PanelParams& p, int m
             float gs[4] = {gq.x, gq.y, gq.z, gq.w};
             const double dgv[4] = {dq01.x, dq01.y, dq23.x, dq23.y};
             const double rcv[4] = {rq01.x, rq01.y, rq23.x, rq23.y};
-            panel_shrink4<DS, GM>(acc[mt][nt], xs, gs, dgv, rcv, mu, dh, dl, sbx, sx, err);
+            panel_shrink4<DS, GM, POS>(acc[mt][nt], xs, gs, dgv, rcv, mu, dh, dl, sbx, sx, err);
             if constexpr (GM != 0 && (BPGL_PANEL_DIAG & 1) == 0)
                 *reinterpret_cast<float4*>(p.Gc + (long long)rhs * p.w + j) = make_float4(gs[0], gs[1], gs[2], gs[3]);
             if constexpr ((BPGL_PANEL_DIAG & 2) == 0)
@@ -841,9 +871,9 @@ __device__ __forceinline__ void panel_pass1_epilogue(const PanelParams& p, int m
 // ---------------------------------------------------------------------------
 // pass 1: G = A_m^T R (EPI 0: write G [k][w] fp64 -- API), or the fused shrink
 // epilogue (EPI 1: the direction D' in DS bf16 pieces (2: Dh + Dl, 1: Dh alone), norms
-// per RHS).  grid = w / 256 blocks.  R always enters as hi + lo.
+// per RHS).  grid = w / 256 blocks.  R always enters as hi + lo.  POS: the non-negative shrink (panel_shrink4).
 // ---------------------------------------------------------------------------
-template <int NT, int EPI, int ILV, int DS, int GM = 0>
+template <int NT, int EPI, int ILV, int DS, int GM = 0, bool POS = false>
 __global__ __launch_bounds__((PanelGeo<NT, 2>::T)) void k_panel_pass1(PanelParams p, int fixed_block,
                                                                          double* __restrict__ Gout) {
     using G = PanelGeo<NT, 2>;
@@ -860,7 +890,7 @@ __global__ __launch_bounds__((PanelGeo<NT, 2>::T)) void k_panel_pass1(PanelParam
     else
         panel_gemm<NT, 1, ILV, 2>(smem, p.A1t, ld1, 0, (long long)mb * p.w + c0, p.Rh, p.Rl, p.ldr, 0,
                                   (int)(p.m / kPanelK), acc);
-    panel_pass1_epilogue<G::NTW, EPI, DS, GM, G::NW>(p, mb, c0, wm, wn, G::T, acc, smem, Gout);
+    panel_pass1_epilogue<G::NTW, EPI, DS, GM, G::NW, POS>(p, mb, c0, wm, wn, G::T, acc, smem, Gout);
 }
 
 // ---------------------------------------------------------------------------
@@ -1412,6 +1442,10 @@ __global__ __launch_bounds__(kThreads) void k_panel_flush(PanelParams p) {
     for (unsigned u = blockIdx.x * kThreads + threadIdx.x; u < (unsigned)(nx / 8); u += gridDim.x * kThreads)
         panel_x_update8<DS>(p, p.X, u, w8);
 }
+// From here to the end of the file: the kernels that are not templates.  A second translation unit that
+// instantiates kernel variants of its own (bpgl_panel_pos.hip) defines BPGL_PANEL_TEMPLATES_ONLY, so that
+// bpgl_panel_abi.hip stays the one unit that defines them.
+#ifndef BPGL_PANEL_TEMPLATES_ONLY
 __global__ void k_panel_clear_pending(PanelParams p) {
     if (threadIdx.x == 0) p.st->pending = 0;
 }
@@ -1566,5 +1600,6 @@ __global__ void k_panel_reset_state(PanelParams p) {
         p.st->fail = 0;
     }
 }
+#endif  // BPGL_PANEL_TEMPLATES_ONLY
 
 }  // namespace bpgl

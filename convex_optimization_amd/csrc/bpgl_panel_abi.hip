@@ -14,6 +14,7 @@
 #include "bpgl_host.h"
 #include "bpgl_panel.h"
 #include "bpgl_panel_gap.h"
+#include "bpgl_panel_pos.h"
 
 using namespace bpgl;
 using namespace bpgl_host;
@@ -57,6 +58,7 @@ struct bpgl_panel {
     bool masked = false;          // a mask is installed (the caller's, or the intercept's all-ones one): the MK kernel variants run
     bool user_mask = false;       // ... and it is the caller's (bpgl_panel_set_row_mask)
     bool icpt = false;            // bpgl_panel_set_intercept: the intercept (IC) kernel variants run (always with `masked`)
+    bool positive = false;        // bpgl_panel_set_positive: x >= 0 (the POS pass-1 variants, the one-sided certificate)
     bool icpt_valid = false;      // a bpgl_panel_gap has run since the last reset: icpt_host is its beta0
     std::vector<double> icpt_host;
     char* scratch = nullptr;      // the caller's scratch and its layout (bpgl_panel_bind)
@@ -186,6 +188,8 @@ int panel_launch(bpgl_panel* c, int which, int fixed_block, double* out, int mod
                         pass1 = dispatch<1, 2, 0>(c->gm_cur, [](auto gm) {
                             return &k_panel_pass1<NT, 1, ILV, NS, decltype(gm)::value>;
                         });
+                    if (mode && c->positive)   // the POS variant of the same form, from its own code object
+                        pass1 = bpgl_pos::pass1(c->k, ILV, NS, c->gm_cur);
                     hipLaunchKernelGGL(pass1, dim3((unsigned)(c->w / kPanelRows)), dim3(PanelGeo<NT, 2>::T), 0,
                                        c->stream, c->p, fixed_block, out);
                     LAUNCH_CHECK("k_panel_pass1");
@@ -514,7 +518,7 @@ int bpgl_panel_bind(bpgl_panel* c, const void* A, int64_t lda, void* scratch, in
     hipLaunchKernelGGL((k_panel_tile<64, 256, false>), dim3((unsigned)((c->m / 64) * (c->n / 256))), dim3(256), 0,
                        c->stream, p.A, p.lda, c->n, c->at<__bf16>(L.A1t));
     LAUNCH_CHECK("k_panel_tile");
-    c->masked = c->user_mask = c->icpt = c->icpt_valid = false;   // p.W is null again
+    c->masked = c->user_mask = c->icpt = c->icpt_valid = c->positive = false;   // p.W is null again
     panel_fuse_check(c);
     c->bound = true;
     c->have_diag = false;
@@ -597,6 +601,13 @@ int bpgl_panel_reset_x0(bpgl_panel* c, const double* B, const double* mu, const 
         // x = X0 (the stored iterate itself when X0 is bpgl_panel_x), R = A x - B and Ax from the fp64
         // product on that fp32 x, R's images from that R
         if (X0 != p.X) HIP_TRY(hipMemcpyAsync(p.X, X0, xbytes, hipMemcpyDeviceToDevice, c->stream));
+        if (c->positive) {   // the start is max(X0, 0): feasible, and R below is formed from it
+            const int64_t nx = xbytes / 4;
+            hipLaunchKernelGGL(bpgl_pos::project_x(),
+                               dim3((unsigned)std::min<int64_t>(cdiv(nx, kThreads), 2048)), dim3(kThreads), 0, c->stream,
+                               p.X, (long long)nx);
+            LAUNCH_CHECK("k_panel_project_x");
+        }
         if ((rc = panel_warm_residual(c))) return rc;
         if ((rc = panel_split(c, p.R, c->m, c->ldr(), p.Rh, p.Rl, 1.0, nullptr))) return rc;
     }
@@ -749,6 +760,7 @@ int bpgl_panel_get_tuning(const bpgl_panel* c, const char* key, int64_t* value) 
     else if (!strcmp(key, "fuse_update")) *value = c->nblock == 1 && c->defer_x && c->fuse_update && c->fuse_ok;   // in effect
     else if (!strcmp(key, "carry_g")) *value = panel_carry(c) ? 1 : 0;   // the form in effect
     else if (!strcmp(key, "g_refresh")) *value = c->g_period;
+    else if (!strcmp(key, "positive")) *value = c->positive ? 1 : 0;   // bpgl_panel_set_positive
     else return fail(BPGL_E_ARG, "unknown panel tuning key '%s'", key);
     return 0;
 }
@@ -784,6 +796,15 @@ int bpgl_panel_set_intercept(bpgl_panel* c, int on) {
     c->icpt_valid = false;
     if ((rc = panel_install_mask(c))) return rc;
     return panel_run_diag(c);   // centred norms and rec with the intercept, k_panel_diag's without
+}
+
+int bpgl_panel_set_positive(bpgl_panel* c, int on) {
+    int rc;
+    if ((rc = panel_ready(c))) return rc;
+    c->positive = on != 0;
+    c->solver = false;   // the graphs bake the pass-1 variant in: a reset must follow
+    drop_graphs(c);
+    return 0;
 }
 
 int bpgl_panel_intercept(bpgl_panel* c, double* out) {
@@ -829,8 +850,8 @@ int bpgl_panel_gap(bpgl_panel* c, double* G_all, double* R_fresh, uint8_t* keep,
         HIP_TRY(hipEventRecord(c->gap_ev[prod], c->stream));
     }
     const int nparts = pgap_nparts(c);
-    hipLaunchKernelGGL(k_pgap_partials, dim3((unsigned)nparts, (unsigned)c->k), dim3(kThreads), 0, c->stream, a,
-                       parts);
+    hipLaunchKernelGGL(c->positive ? bpgl_pos::gap_partials() : &k_pgap_partials<false>,
+                       dim3((unsigned)nparts, (unsigned)c->k), dim3(kThreads), 0, c->stream, a, parts);
     LAUNCH_CHECK("k_pgap_partials");
     hipLaunchKernelGGL(k_pgap_final, dim3((unsigned)c->k), dim3(kThreads), 0, c->stream, parts, nparts, a.mu, res);
     LAUNCH_CHECK("k_pgap_final");
@@ -841,8 +862,8 @@ int bpgl_panel_gap(bpgl_panel* c, double* G_all, double* R_fresh, uint8_t* keep,
     }
     if (keep) {
         const int64_t nb = cdiv(c->n, kThreads);
-        hipLaunchKernelGGL(k_pgap_screen, dim3((unsigned)nb, (unsigned)c->k), dim3(kThreads), 0, c->stream, a, res, keep,
-                           counts);
+        hipLaunchKernelGGL(c->positive ? bpgl_pos::gap_screen() : &k_pgap_screen<false>,
+                           dim3((unsigned)nb, (unsigned)c->k), dim3(kThreads), 0, c->stream, a, res, keep, counts);
         LAUNCH_CHECK("k_pgap_screen");
         hipLaunchKernelGGL(k_pgap_count, dim3((unsigned)c->k), dim3(kThreads), 0, c->stream, counts, (long long)nb, res);
         LAUNCH_CHECK("k_pgap_count");

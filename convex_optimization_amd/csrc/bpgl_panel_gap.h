@@ -34,6 +34,11 @@
 //   k_pgap_centre           Rf = in ? Rf - c' : 0, i.e. P_w(A x - b); the held-out (e - c)^2 = (a.x + beta0 - b)^2,
 //                           squared directly, to the per-block partials that k_pgap_holdout consumes
 // Product 2 and everything after it read the centred Rf: the certificate of the profiled problem.
+// With the non-negative constraint (bpgl_panel_set_positive; the POS variants, which only
+// bpgl_panel_pos.hip instantiates):
+//   k_pgap_partials         max |g| becomes max_j (-g_j)+, so scale = min(1, mu / that) makes scale r feasible for the
+//                           one-sided dual constraint -a_j . theta <= mu; primal, dual and gap keep their formulas
+//   k_pgap_screen           score_j = scale (-g_j) + sqrt(d_j) sqrt(2 max(gap, 0))
 // Every reduction walks its dimension in a fixed order (within a chunk: 32-deep stages in index
 // order, 4 at a time through the MFMA; then the chunks; then wave_sum / wave_max, the waves, the
 // blocks in index order).  No floating-point atomics: two calls on the same state return the same
@@ -47,6 +52,7 @@
 
 #include "bpgl_panel.h"
 
+// (The kernels that are not templates sit under BPGL_PANEL_TEMPLATES_ONLY guards: see bpgl_panel.h.)
 namespace bpgl {
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
@@ -241,6 +247,7 @@ __global__ __launch_bounds__(kThreads) void k_pgap_fold(PanelGapArgs a) {
     }
 }
 
+#ifndef BPGL_PANEL_TEMPLATES_ONLY
 // intercept, one block per RHS: the nb fold blocks' in-row sums added in block order (loaded kThreads at a
 // time, thread 0 adding them in index order) -> icp[0][k] = c' = sum / n_w (0 for an all-zero mask column),
 // icp[1][k] = beta0 = bmean - c' = -mean_in(a_i . x - b_i)
@@ -281,6 +288,7 @@ __global__ __launch_bounds__(kThreads) void k_pgap_centre(PanelGapArgs a) {
     __syncthreads();
     if (threadIdx.x == 0) a.hpart[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
 }
+#endif  // BPGL_PANEL_TEMPLATES_ONLY
 
 // bpgl_panel_reset_x0 with more than one feature block: product 1 ran with its
 // chunks aligned to the feature blocks (a.spl = nblock x spb, chunk c inside block c / spb).  One thread
@@ -307,6 +315,7 @@ __global__ __launch_bounds__(kThreads) void k_pgap_fold_ax(PanelGapArgs a, int s
     R[e] = in ? acc - a.B[e] : 0.0;
 }
 
+#ifndef BPGL_PANEL_TEMPLATES_ONLY
 // one block per RHS: res[k][7] = the held-out partials of its nb fold blocks, thread q taking blocks
 // q, q + kThreads, ... in order and thread 0 adding the threads' sums in thread order
 __global__ __launch_bounds__(kThreads) void k_pgap_holdout(const double* __restrict__ hpart, long long nb,
@@ -322,8 +331,11 @@ __global__ __launch_bounds__(kThreads) void k_pgap_holdout(const double* __restr
     for (int q = 0; q < kThreads; ++q) tot += red[q];
     res_all[(long long)k * kPgRes + 7] = tot;
 }
+#endif  // BPGL_PANEL_TEMPLATES_ONLY
 
-// grid (nparts, k); parts[k][nparts][kPgPart]
+// grid (nparts, k); parts[k][nparts][kPgPart].  POS: the dual constraint is one-sided, -a_j . theta <= mu, and
+// the fourth partial is max (-g)+ instead of max |g|
+template <bool POS = false>
 __global__ __launch_bounds__(kThreads) void k_pgap_partials(PanelGapArgs a, double* __restrict__ parts) {
     const int k = blockIdx.y;
     const long long tid = (long long)blockIdx.x * kThreads + threadIdx.x;
@@ -341,7 +353,12 @@ __global__ __launch_bounds__(kThreads) void k_pgap_partials(PanelGapArgs a, doub
     for (long long j = tid; j < a.n; j += stride) {
         const long long e = ((j / a.w) * a.k + k) * a.w + j % a.w;
         ax += fabs((double)a.X[e]);
-        gm = nan_max(gm, fabs(a.G[e]));
+        if constexpr (POS) {
+            const double gv = a.G[e];
+            gm = nan_max(gm, gv > 0.0 ? 0.0 : -gv);   // (a NaN stays a NaN)
+        } else {
+            gm = nan_max(gm, fabs(a.G[e]));
+        }
     }
     rr = wave_sum(rr);
     rb = wave_sum(rb);
@@ -360,6 +377,7 @@ __global__ __launch_bounds__(kThreads) void k_pgap_partials(PanelGapArgs a, doub
     }
 }
 
+#ifndef BPGL_PANEL_TEMPLATES_ONLY
 // one block per RHS; thread q holds partial q (nparts <= kPgPartBlocks = kThreads).  The formulas and
 // the NaN behaviour of k_gap_final.
 __global__ __launch_bounds__(kThreads) void k_pgap_final(const double* __restrict__ parts, int nparts,
@@ -403,8 +421,11 @@ __global__ __launch_bounds__(kThreads) void k_pgap_final(const double* __restric
     res[6] = dr;
     res[7] = 0.0;
 }
+#endif  // BPGL_PANEL_TEMPLATES_ONLY
 
-// grid (ceil(n / kThreads), k): keep[k][j] for the global column j; counts[k][block] = columns kept
+// grid (ceil(n / kThreads), k): keep[k][j] for the global column j; counts[k][block] = columns kept.
+// POS: score_j = scale (-g_j) + ...
+template <bool POS = false>
 __global__ __launch_bounds__(kThreads) void k_pgap_screen(PanelGapArgs a, const double* __restrict__ res_all,
                                                           unsigned char* __restrict__ keep,
                                                           int* __restrict__ counts) {
@@ -416,7 +437,7 @@ __global__ __launch_bounds__(kThreads) void k_pgap_screen(PanelGapArgs a, const 
         const double gap = res[2], s = res[3];
         const double gp = gap < 0.0 ? 0.0 : gap;   // a NaN stays a NaN
         const double g = a.G[((j / a.w) * a.k + k) * a.w + j % a.w];
-        const double score = s * fabs(g) + sqrt(a.diag[j]) * sqrt(2.0 * gp);
+        const double score = s * (POS ? -g : fabs(g)) + sqrt(a.diag[j]) * sqrt(2.0 * gp);
         kp = !(score < a.mu[k]);
         keep[(long long)k * a.n + j] = kp ? 1 : 0;
     }
@@ -428,6 +449,7 @@ __global__ __launch_bounds__(kThreads) void k_pgap_screen(PanelGapArgs a, const 
     if (threadIdx.x == 0) counts[(long long)k * gridDim.x + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
 }
 
+#ifndef BPGL_PANEL_TEMPLATES_ONLY
 // one block per RHS: res[k][5] = sum of its per-block counts (integers: exact in any order)
 __global__ __launch_bounds__(kThreads) void k_pgap_count(const int* __restrict__ counts, long long nblocks,
                                                          double* __restrict__ res_all) {
@@ -442,5 +464,6 @@ __global__ __launch_bounds__(kThreads) void k_pgap_count(const int* __restrict__
     for (int q = 0; q < kThreads; ++q) tot += red[q];
     res_all[(long long)k * kPgRes + 5] = (double)tot;
 }
+#endif  // BPGL_PANEL_TEMPLATES_ONLY
 
 }  // namespace bpgl

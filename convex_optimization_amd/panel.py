@@ -38,6 +38,9 @@ gap-safe screen proves zero for every right-hand side.
 ``PanelLasso.set_intercept`` gives every right-hand side an unpenalised intercept, centred over that
 right-hand side's own in-rows inside the fold, and ``lasso_path`` / ``lasso_cv`` take ``fit_intercept``
 (DESIGN.md section 13).
+``PanelLasso.set_positive`` adds the sign constraint x >= 0 (scikit-learn's ``positive=True``, glmnet's
+``lower.limits = 0``) to every right-hand side -- every stored iterate is then >= 0 -- and ``lasso_path`` /
+``lasso_cv`` take ``positive``.
 
 All compute goes through libbpgl.so (bpgl_panel_* in include/bpgl.h).
 """
@@ -78,6 +81,7 @@ _PANEL_SIGS = {
     "bpgl_panel_gather_columns": (ctypes.c_int, [_p, _p, _i64, _p, _i64]),
     "bpgl_panel_set_intercept": (ctypes.c_int, [_p, ctypes.c_int]),
     "bpgl_panel_intercept": (ctypes.c_int, [_p, ctypes.POINTER(ctypes.c_double)]),
+    "bpgl_panel_set_positive": (ctypes.c_int, [_p, ctypes.c_int]),
 }
 N._SIGS.update(_PANEL_SIGS)
 
@@ -274,6 +278,14 @@ class PanelLasso:
             N.check(_lib().bpgl_panel_diag(self._ctx, N.ptr(self._diag)), "bpgl_panel_diag")   # the diag in effect
         self._intercept = bool(on)
 
+    def set_positive(self, on):
+        """The sign constraint x >= 0 on every right-hand side (bpgl_panel_set_positive): each column minimises
+        1/2 ||w o (A x - b)||^2 + mu sum x subject to x >= 0 (with the row mask and the intercept when those are
+        on).  A ``solver_reset`` must follow; with ``x0`` it starts at max(x0, 0).  Every stored iterate is
+        >= 0, ``duality_gap`` certifies the constrained problem (gnorm_inf is then max_j (-g_j)+ and the screen
+        one-sided), and ``set_positive(False)`` restores the plain solver bitwise."""
+        N.check(_lib().bpgl_panel_set_positive(self._ctx, int(bool(on))), "bpgl_panel_set_positive")
+
     def solver_step(self, n_iter):
         with self._on_stream():
             N.check(_lib().bpgl_panel_step(self._ctx, int(n_iter)), "bpgl_panel_step")
@@ -426,14 +438,26 @@ def _check_shrink(shrink):
     return float(shrink)
 
 
-def _screened_loop(pl, B, mu, target, ITER_MAX, check_every, shrink, mask=None, intercept=False):
+def _grid_below(mu_max, n_mus, hi, lo, positive):
+    """``mu_grid`` below the mu_max read off the x = 0 certificate, for every path and CV run.  With ``positive``
+    mu_max is max_j (a_j . b)+, and 0 means that no column correlates positively with b: x = 0 solves every
+    mu > 0, and a grid of zeros would be built -- ValueError instead.  (A NaN mu_max is passed on, as without the
+    flag: it is not this condition.)"""
+    from .cpu_calculation import mu_grid
+    if positive and float(mu_max) <= 0.0:
+        raise ValueError("positive=True: no column of A correlates positively with b (mu_max = 0); "
+                         "x = 0 is the solution for every mu")
+    return mu_grid(float(mu_max), n_mus, hi, lo)
+
+
+def _screened_loop(pl, B, mu, target, ITER_MAX, check_every, shrink, mask=None, intercept=False, positive=False):
     """``_check_loop`` on a freshly reset ``pl`` (reset with ``B``, ``mu``; ``mask``: the (m, k) row mask
     installed on it, or None) with gap-safe compaction, ``ClassLassoScreened``'s rule on a panel: after
     a check that did not stop the loop, the union over the panel's columns of the screen's keep goes
     through ``cpu_calculation.compaction_columns`` with q = Block * 256; when that leaves at most
     ``shrink`` times the active columns, they are gathered (``gather_columns``), a new ``PanelLasso`` of
-    the same Block and width is built over them, the mask (and, with ``intercept``, the intercept, which
-    ``pl`` then has on too) installed there, and the solve continues
+    the same Block and width is built over them, the mask (and, with ``intercept`` / ``positive``, the
+    intercept / the sign constraint, which ``pl`` then has on too) installed there, and the solve continues
     from ``solver_reset(B, mu, x0=X[sel])``.  ``pl`` stays alive; an earlier narrow context is dropped.
 
     Returns dict(t, cert, first, reached, x (n, k), active, compactions [(t, n_active after)],
@@ -468,6 +492,8 @@ def _screened_loop(pl, B, mu, target, ITER_MAX, check_every, shrink, mask=None, 
             nxt = PanelLasso(cur.gather_columns(sel_d), pl.Block, nrhs=k, device=pl.device)
             if intercept:
                 nxt.set_intercept(True)
+            if positive:
+                nxt.set_positive(True)
             if mask is not None:
                 nxt.set_row_mask(mask)
             nxt.solver_reset(B, mu, x0=x0)
@@ -491,7 +517,7 @@ def _screened_loop(pl, B, mu, target, ITER_MAX, check_every, shrink, mask=None, 
 
 
 def lasso_path(A, b, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_BOUND=1e-4, ITER_MAX=4096,
-               check_every=PATH_CHECK_EVERY, device=None, x0=None, shrink=0.0, fit_intercept=False):
+               check_every=PATH_CHECK_EVERY, device=None, x0=None, shrink=0.0, fit_intercept=False, positive=False):
     """A regularization path as ONE panel: min 1/2 ||A x - b||^2 + mu ||x||_1 for every mu of a grid,
     on the bf16-stored A, every column of the panel holding the same b.
 
@@ -520,8 +546,12 @@ def lasso_path(A, b, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_BOUND=1e-4
     ``fit_intercept`` (``Block`` must be 1, ValueError otherwise): every mu solves
     min over x, beta0 of 1/2 ||A x + beta0 - b||^2 + mu ||x||_1 (``PanelLasso.set_intercept``, also on
     every narrower context of ``shrink``).  mu_max is then ||A^T (b - mean b)||_inf, the bound
-    GAP_BOUND * 1/2 ||b - mean b||^2, and ``intercept`` (len(mus),) is returned (zeros without it)."""
-    from .cpu_calculation import mu_grid
+    GAP_BOUND * 1/2 ||b - mean b||^2, and ``intercept`` (len(mus),) is returned (zeros without it).
+
+    ``positive``: every mu solves the problem subject to x >= 0
+    (``PanelLasso.set_positive``, also on every narrower context of ``shrink``); the returned x is >= 0
+    elementwise, an ``x0`` is projected to max(x0, 0), and with ``mus=None`` mu_max is max_j (a_j . b)+
+    (ValueError when that is 0: no column correlates positively with b)."""
     if int(check_every) <= 0:
         raise ValueError("check_every must be > 0")
     shrink = _check_shrink(shrink)
@@ -546,12 +576,14 @@ def lasso_path(A, b, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_BOUND=1e-4
     pl = PanelLasso(A, Block, nrhs=k, device=device)
     if fit_intercept:
         pl.set_intercept(True)
+    if positive:
+        pl.set_positive(True)
     B = np.repeat(b[:, None], k, axis=1)
     mu_max = None
     if grid is None:
         pl.solver_reset(B, 1.0)
         mu_max = float(pl.duality_gap(screen=False)["gnorm_inf"][0])
-        grid, _ = pad_mus(mu_grid(mu_max, n_given, hi, lo))
+        grid, _ = pad_mus(_grid_below(mu_max, n_given, hi, lo, positive))
     if x0 is None:
         pl.solver_reset(B, grid)
     else:
@@ -559,7 +591,8 @@ def lasso_path(A, b, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_BOUND=1e-4
         pl.solver_reset(B, grid, x0=np.concatenate([x0, pad], axis=1))
     bc = b - b.mean() if fit_intercept else b
     target = float(GAP_BOUND) * 0.5 * float(bc @ bc)
-    run = _screened_loop(pl, B, grid, target, ITER_MAX, check_every, shrink, intercept=bool(fit_intercept))
+    run = _screened_loop(pl, B, grid, target, ITER_MAX, check_every, shrink, intercept=bool(fit_intercept),
+                         positive=bool(positive))
     cert = run["cert"]
     out = dict(x=run["x"][:, :n_given], mus=grid[:n_given].copy(), mu_max=mu_max, iters=run["t"],
                reached=run["reached"][:n_given], first_reached=run["first"][:n_given])
@@ -572,7 +605,7 @@ def lasso_path(A, b, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_BOUND=1e-4
 
 def lasso_cv(A, b, n_folds=8, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_BOUND=1e-4, ITER_MAX=4096,
              check_every=PATH_CHECK_EVERY, seed=0, masks=None, refit=True, return_x=False, device=None,
-             shrink=0.0, warm_refit=False, fit_intercept=False):
+             shrink=0.0, warm_refit=False, fit_intercept=False, positive=False):
     """K-fold cross-validation over a grid of mu as ONE panel on one bound A: column c = f * n_mus + j
     solves fold f (the rows of ``masks[f]``) at ``mus[j]``, min 1/2 ||w_f o (A x - b)||^2 + mu_j ||x||_1,
     through ``PanelLasso.set_row_mask``.  n_folds * n_mus <= 128 and n_folds >= 2 (ValueError
@@ -606,8 +639,13 @@ def lasso_cv(A, b, n_folds=8, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_B
     (``PanelLasso.set_intercept``); the refit and every narrower context of ``shrink`` get it too.  mu_max
     is then ||A^T (b - mean b)||_inf, the bound GAP_BOUND * 1/2 ||P_w b||^2 (b centred over the fold's
     training rows), mse scores a_i . x + beta0 against b_i, and ``intercept_folds`` (n_folds, n_mus) and,
-    with ``refit``, ``intercept`` (n_mus,) are returned."""
-    from .cpu_calculation import kfold_masks, mu_grid
+    with ``refit``, ``intercept`` (n_mus,) are returned.
+
+    ``positive``: every column solves its fold subject to x >= 0
+    (``PanelLasso.set_positive``); the refit and every narrower context of ``shrink`` get it too, the
+    ``warm_refit`` start (a mean of non-negative solutions) is non-negative, and with ``mus=None`` mu_max is
+    max_j (a_j . b)+ (ValueError when that is 0)."""
+    from .cpu_calculation import kfold_masks
     if int(check_every) <= 0:
         raise ValueError("check_every must be > 0")
     shrink = _check_shrink(shrink)
@@ -637,10 +675,13 @@ def lasso_cv(A, b, n_folds=8, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_B
     pl = PanelLasso(A, Block, nrhs=k, device=device)
     if fit_intercept:
         pl.set_intercept(True)
+    positive = bool(positive)
+    if positive:
+        pl.set_positive(True)
     B = np.repeat(b[:, None], k, axis=1)
     if mus is None:
         pl.solver_reset(B, 1.0)
-        mus = mu_grid(float(pl.duality_gap(screen=False)["gnorm_inf"][0]), n_mus, hi, lo)
+        mus = _grid_below(float(pl.duality_gap(screen=False)["gnorm_inf"][0]), n_mus, hi, lo, positive)
     cols = np.concatenate([np.arange(ncol), np.zeros(k - ncol, dtype=np.int64)])   # the pad: copies of column 0
     fold, jmu = cols // n_mus, cols % n_mus
     pl.set_row_mask(masks[fold].T)
@@ -650,7 +691,7 @@ def lasso_cv(A, b, n_folds=8, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_B
     bb = np.array([float(centred(masks[f].astype(np.float64), b) @ centred(masks[f].astype(np.float64), b))
                    for f in range(n_folds)])
     run = _screened_loop(pl, B, mus[jmu], float(GAP_BOUND) * 0.5 * bb[fold], ITER_MAX, check_every, shrink,
-                         mask=masks[fold].T, intercept=fit_intercept)
+                         mask=masks[fold].T, intercept=fit_intercept, positive=positive)
     t, cert = run["t"], run["cert"]
     shape = (n_folds, n_mus)
     count = (masks == 0).sum(axis=1).astype(np.float64)
@@ -679,7 +720,7 @@ def lasso_cv(A, b, n_folds=8, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_B
             pl.solver_reset(B, grid)
         bc = b - b.mean() if fit_intercept else b
         rrun = _screened_loop(pl, B, grid, float(GAP_BOUND) * 0.5 * float(bc @ bc), ITER_MAX, check_every, shrink,
-                              intercept=fit_intercept)
+                              intercept=fit_intercept, positive=positive)
         out.update(x=rrun["x"][:, :n_mus], refit_gap=rrun["cert"]["gap"][:n_mus], refit_iters=rrun["t"],
                    refit_compactions=rrun["compactions"])
         if fit_intercept:

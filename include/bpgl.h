@@ -90,7 +90,12 @@ const char* bpgl_last_error(void);
  *                different centrings still share one bound A).  Opt-in: with it off
  *                every kernel that existed is unchanged.  bpgl_panel_scratch_bytes grows by the pieces
  *                laid out after everything that existed (one more line-search partial per 1024-row group,
- *                a few nrhs-long vectors, the certificate's in-row partials). */
+ *                a few nrhs-long vectors, the certificate's in-row partials).
+ *   308 (0.3.8): + bpgl_panel_set_positive (the sign constraint x >= 0 per right-hand side: the one-sided
+ *                prox, a feasible bf16 direction image, the one-sided certificate and screen; DESIGN.md
+ *                section 14) and the panel tuning key "positive" (bpgl_panel_get_tuning only).  Opt-in:
+ *                with it off every kernel that existed is unchanged, bit for bit.
+ *                bpgl_panel_scratch_bytes does not change. */
 int bpgl_version(void);
 
 /*
@@ -534,6 +539,31 @@ int bpgl_panel_set_intercept(bpgl_panel* ctx, int on);
  * (and no such requirement) with the intercept off.
  */
 int bpgl_panel_intercept(bpgl_panel* ctx, double* out);
+/*
+ * Non-negative lasso (since ABI 308): with `on` nonzero every right-hand side solves
+ *   min 1/2 || w_k o (A x - b_k) ||^2 + mu_k sum_j x_j   subject to x >= 0
+ * (with the row mask and / or the intercept's profiling when those are installed).  Only the pass-1 shrink
+ * changes: the prox is the one-sided threshold x^_j = max(0, S(d_j x_j - g_j, mu) / d_j), and the direction's
+ * bf16 image D' is made feasible -- where the nearest image has x + D' < 0 (a coordinate sent to 0:
+ * bf16(-x) can exceed x in magnitude) it is replaced by its neighbour towards zero (d_split 1), or the lo
+ * piece is moved one step up (d_split 2), so that x + D' >= 0 in the fp64 arithmetic that applies it.  The
+ * step size lies in [0, 1], so EVERY stored iterate is >= 0 (no clamp after the update: R is a recurrence and
+ * must stay A dx).  Pass 2, the fold, the line search (sum |x + D'| is sum (x + D')) and the updates are the
+ * unchanged kernels.  The error record is the constrained prox residual max |x - max(0, x - g - mu)|.
+ * bpgl_panel_gap then certifies the constrained problem: the dual constraint is one-sided, -a_j . theta <= mu,
+ * so out[8 k + 4] is max_j (-g_j)+ instead of ||g||_inf, scale = min(1, mu / that) (1 when it is 0), primal,
+ * dual and gap keep their formulas, and the screen is score_j = scale (-g_j) + sqrt(d_j) sqrt(2 max(gap, 0)),
+ * keep_j = !(score_j < mu).  At x = 0 out[8 k + 4] is max_j (a_j . b)+: above it x = 0 is optimal.
+ * drift, the held-out sum of squares and the intercept keep their meaning.
+ * bpgl_panel_reset_x0 with the constraint on starts at X = max(X0, 0) elementwise -- X0 bitwise where
+ * X0 >= 0 (-0 becomes +0), also for the in-place restart X0 == bpgl_panel_x(ctx) -- and forms R from that
+ * projected X, so a certificate right after it reports drift 0 (one feature block).
+ * It invalidates the solver and drops the graphs exactly as bpgl_panel_set_row_mask does (bpgl_panel_step /
+ * bpgl_panel_gap return BPGL_E_STATE until the next reset); bpgl_panel_bind switches it off.
+ * bpgl_panel_get_tuning("positive") reports it.  With it off every result is bitwise what ABI 307 computes.
+ * Legal any time after bpgl_panel_bind (BPGL_E_STATE before it; BPGL_E_ARG on a null context).
+ */
+int bpgl_panel_set_positive(bpgl_panel* ctx, int on);
 /*
  * Warm start (since ABI 306): bpgl_panel_reset at a given iterate.
  * X0: device fp32 [nblock][nrhs][w] (the layout of bpgl_panel_x), 16-byte aligned, caller-owned.

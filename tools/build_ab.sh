@@ -12,8 +12,10 @@ else
   git -C $R archive $REF convex_optimization_amd/csrc include | tar -x -C $SRC
 fi
 mkdir -p $R/build_ab
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared "$@" -I$SRC/include \
-    $SRC/convex_optimization_amd/csrc/bpgl.hip $SRC/convex_optimization_amd/csrc/bpgl_panel_abi.hip \
+# the library's translation units: the Makefile's; a ref from before ABI 308 has no bpgl_panel_pos.hip
+UNITS="$SRC/convex_optimization_amd/csrc/bpgl.hip $SRC/convex_optimization_amd/csrc/bpgl_panel_abi.hip"
+[ -f $SRC/convex_optimization_amd/csrc/bpgl_panel_pos.hip ] && UNITS="$UNITS $SRC/convex_optimization_amd/csrc/bpgl_panel_pos.hip"
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared "$@" -I$SRC/include $UNITS \
     -o $R/build_ab/$NAME.so -lrccl
 rm -rf $SRC
 echo "built build_ab/$NAME.so from $REF"
