@@ -23,7 +23,9 @@ restatement of the panel's row-masked problems (K-fold cross-validation, DESIGN.
 ``compaction_columns``, the columns a screened panel keeps when it is compacted (DESIGN.md section 12);
 ``centred_diag``, ``intercept_panel_iterate`` and ``intercept_duality_gap``, the restatement of the
 panel's intercept; ``positive_panel_iterate`` and ``positive_duality_gap``, the
-restatement of the panel's non-negative lasso (x >= 0).
+restatement of the panel's non-negative lasso (x >= 0); ``penalty_panel_iterate`` and
+``penalty_duality_gap``, the restatement of the panel's penalty factors (per-column l1 weights, DESIGN.md
+section 15).
 """
 import numpy as np
 
@@ -383,6 +385,114 @@ def positive_duality_gap(A, b, w, x, mu, diag=None, intercept=False):
     score = scale * (-g) + np.sqrt(dg) * np.sqrt(2.0 * np.maximum(gap, 0.0))
     return dict(primal=primal, dual=dual, gap=gap, scale=scale, gnorm_inf=gn, holdout_sse=float(h @ h),
                 intercept=-c if (intercept and nw > 0) else 0.0, score=score, keep=~(score < mu), g=g, r=r)
+
+
+# ---------------------------------------------------------------------------
+# Penalty factors: min 1/2 || w o (A x - b) ||^2 + mu sum_j p_j |x_j| with p_j > 0, with or
+# without the intercept's profiling and the sign constraint.  The host restatement of bpgl_panel_set_penalty's
+# solver and certificate.  The factors are used as given (no renormalisation to sum p = n).
+# ---------------------------------------------------------------------------
+def _penalty(p, n):
+    p = np.asarray(p, dtype=np.float64).reshape(-1)
+    if p.size != n or not np.all(np.isfinite(p) & (p > 0.0)):
+        raise ValueError("penalty factors: n entries, each finite and > 0")
+    return p
+
+
+def penalty_panel_iterate(A, b, w, mu, p, Block, iters, diag=None, x0=None, intercept=False, positive=False):
+    """``iters`` block updates (cyclic over ``Block`` feature blocks; ``intercept`` needs Block = 1) of the
+    panel's iteration on the weighted problem of one right-hand side, in fp64: R = w o (A x - b) (P_w (A x - b)
+    with ``intercept``), G = A_m^T R, the prox x^_j = S(d_j x_j - G_j, mu p_j) / d_j (max(0, .) with ``positive``;
+    0 where d_j = 0), D = x^ - x, S = w o (A_m D), the exact line search of the weighted objective along D,
+    gamma = clip(-(R.S + mu (sum p |x + D| - sum p |x|)) / |P S|^2, 0, 1), and x += gamma D.  ``p``: (n,), every
+    entry finite and > 0 (ValueError otherwise).  ``w`` None: all rows.  ``diag``: default the full column norms
+    (``centred_diag(A)`` with ``intercept``).  With ``positive`` ``x0`` is projected to max(x0, 0).  Returns
+    dict(x, r[, intercept])."""
+    A = np.asarray(A, dtype=np.float64)
+    m, n = A.shape
+    Block = int(Block)
+    if intercept and Block != 1:
+        raise ValueError("intercept needs Block = 1")
+    wd = n // Block
+    b = np.asarray(b, dtype=np.float64).reshape(-1)
+    w = np.ones(m) if w is None else (np.asarray(w).reshape(-1) != 0).astype(np.float64)
+    nw = float(w.sum())
+    mu = float(mu)
+    pw = _penalty(p, n).reshape(Block, wd)
+    if diag is None:
+        dg = centred_diag(A) if intercept else np.square(A).sum(axis=0)
+    else:
+        dg = np.asarray(diag, dtype=np.float64).reshape(-1)
+    with np.errstate(divide="ignore"):
+        rec = np.where(dg > 0, 1.0 / np.where(dg > 0, dg, 1.0), 0.0).reshape(Block, wd)
+    dg = dg.reshape(Block, wd)
+    x = np.zeros(n) if x0 is None else np.array(x0, dtype=np.float64).reshape(-1)
+    if positive:
+        x = np.maximum(x, 0.0)
+    x = x.reshape(Block, wd).copy()
+    proj = (lambda v: _centre(w, v)) if intercept else (lambda v: w * v)
+    R = proj(A @ x.reshape(-1) - b)
+    for t in range(int(iters)):
+        mb = t % Block
+        Am = A[:, mb * wd:(mb + 1) * wd]
+        g = Am.T @ R
+        rx = dg[mb] * x[mb] - g
+        Bx = rec[mb] * (np.sign(rx) * np.maximum(np.abs(rx) - mu * pw[mb], 0))
+        if positive:
+            Bx = np.maximum(Bx, 0.0)
+        D = Bx - x[mb]
+        s = w * (Am @ D)
+        ps = proj(Am @ D)
+        # sum p (|x + D| - |x|) coordinate by coordinate, sign(x) D where the step keeps the sign: the two sums'
+        # difference would lose the O(|D|^2) that is left of r1 near the optimum
+        l1d = np.where(x[mb] * Bx > 0, np.sign(x[mb]) * D, np.abs(Bx) - np.abs(x[mb]))
+        r1 = R @ s + mu * float(pw[mb] @ l1d)
+        r2 = ps @ ps
+        gamma = 0.0 if r2 <= 0 else float(np.clip(-r1 / r2, 0, 1))
+        x[mb] = x[mb] + gamma * D
+        R = R + gamma * ps
+    out = dict(x=x.reshape(-1), r=R)
+    if intercept:
+        e = A @ out["x"] - b
+        out["intercept"] = -(float(w @ e) / nw) if nw > 0 else 0.0
+    return out
+
+
+def penalty_duality_gap(A, b, w, x, mu, p, diag=None, intercept=False, positive=False):
+    """The certificate of the weighted problem at x (x >= 0 with ``positive``): r = w o (A x - b) (P_w (A x - b)
+    with ``intercept``), g = A^T r.  The dual constraint is |a_j . theta| <= mu p_j (-a_j . theta <= mu p_j with
+    ``positive``), so gnorm_inf is max_j |g_j| / p_j (max_j (-g_j)+ / p_j), scale = min(1, mu / that) (1 when it
+    is 0) makes scale r dual feasible, and primal = 1/2 |r|^2 + mu sum p_j |x_j|, dual = -1/2 scale^2 |r|^2 -
+    scale r.b, gap = primal - dual.  At x = 0 gnorm_inf is mu_max = max_j |a_j . b| / p_j.  The gap-safe score is
+    scale |g_j| + sqrt(d_j) sqrt(2 max(gap, 0)) (-g_j for |g_j| with ``positive``), keep_j = not (score_j <
+    mu p_j).  ``w`` None: all rows; ``diag``: default the full column norms (``centred_diag(A)`` with
+    ``intercept``).  Also holdout_sse and intercept as in ``masked_duality_gap`` / ``intercept_duality_gap``."""
+    A = np.asarray(A, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64).reshape(-1)
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    w = np.ones(A.shape[0]) if w is None else (np.asarray(w).reshape(-1) != 0).astype(np.float64)
+    nw = float(w.sum())
+    mu = float(mu)
+    p = _penalty(p, A.shape[1])
+    e = A @ x - b
+    c = (float(w @ e) / nw if nw > 0 else 0.0) if intercept else 0.0
+    r = w * (e - c)
+    g = A.T @ r
+    rr = float(r @ r)
+    primal = 0.5 * rr + mu * float(p @ np.abs(x))
+    ga = np.where(g > 0, 0.0, -g) if positive else np.abs(g)
+    gn = float(np.max(ga / p))       # NaN propagates
+    scale = min(1.0, mu / gn) if gn > 0.0 else 1.0
+    dual = -0.5 * scale * scale * rr - scale * float(r @ b)
+    gap = primal - dual
+    h = (1.0 - w) * (e - c)
+    if diag is None:
+        dg = centred_diag(A) if intercept else np.square(A).sum(axis=0)
+    else:
+        dg = np.asarray(diag, dtype=np.float64).reshape(-1)
+    score = scale * (-g if positive else np.abs(g)) + np.sqrt(dg) * np.sqrt(2.0 * np.maximum(gap, 0.0))
+    return dict(primal=primal, dual=dual, gap=gap, scale=scale, gnorm_inf=gn, holdout_sse=float(h @ h),
+                intercept=-c if (intercept and nw > 0) else 0.0, score=score, keep=~(score < mu * p), g=g, r=r)
 
 
 # ---------------------------------------------------------------------------

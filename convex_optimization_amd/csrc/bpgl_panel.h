@@ -500,6 +500,24 @@ __device__ __forceinline__ u32x4 lds_rd128(unsigned addr) {
     return v;
 }
 
+// ... at addr + OFF + q * STRIDE (q = 0..3, a constant once the caller's loop is unrolled), the offset in the
+// instruction: one address register serves every read of a step, and of the steps of the other column groups
+template <int OFF>
+__device__ __forceinline__ u32x4 lds_rd128o(unsigned addr) {
+    u32x4 v;
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
+    return v;
+}
+template <int STRIDE, int OFF>
+__device__ __forceinline__ u32x4 lds_rd128q(unsigned addr, int q) {
+    switch (q) {
+    case 0: return lds_rd128o<OFF>(addr);
+    case 1: return lds_rd128o<OFF + STRIDE>(addr);
+    case 2: return lds_rd128o<OFF + 2 * STRIDE>(addr);
+    default: return lds_rd128o<OFF + 3 * STRIDE>(addr);
+    }
+}
+
 // x += gamma D' on N consecutive elements of one RHS, D' = hq (+ lq when DS = 2) as the MFMA saw it (V: a
 // vector of N bf16).  Returns whether any element can have changed (x + gamma * 0 is x), which the
 // epilogue forms use to leave unchanged columns' stored x alone.  Every place that applies the x update
@@ -551,18 +569,24 @@ __device__ __forceinline__ __bf16 bf16_next_up(__bf16 h) {
 // -x one bf16 step up (the image itself with DS = 1, its lo piece with DS = 2; one step suffices: the
 // nearest image r of v >= -x has its upper neighbour r' >= v); err is the constrained prox residual
 // |x - max(0, x - g - mu)|.  x >= 0 on entry (the reset projects X0), so every stored iterate stays >= 0.
-template <int DS, int GM, bool POS = false>
+// PF (bpgl_panel_set_penalty): column j pays mu p_j |x_j|; pnv holds the lane's four p_j
+// (not read otherwise).  The threshold of the prox and of err is tau = mu p_j and the two norms are the weighted
+// ones, sum p_j |.|, so that the line search's rs + mu (sbx - sx) stays the exact one of the weighted objective.
+// p = 1 gives the PF = false results bitwise: mu * 1.0 and 1.0 * |x| are exact, also under an fma.
+template <int DS, int GM, bool POS = false, bool PF = false>
 __device__ __forceinline__ void panel_shrink4(const f32x4& acc, const float (&xs)[4], float (&gs)[4],
                                               const double (&dgv)[4], const double (&rcv)[4], double mu,
                                               __bf16 (&dh)[4], __bf16 (&dl)[4], double& sbx, double& sx,
-                                              double& err) {
+                                              double& err, const double (&pnv)[4]) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
+        double tau = mu;
+        if constexpr (PF) tau = mu * pnv[r];
         double g = (double)acc[r];
         if constexpr (GM == 2) g = (double)gs[r] + g;
         if constexpr (GM != 0) gs[r] = (float)g;
         const double x = (double)xs[r];
-        double bx = rcv[r] * soft_thr(dgv[r] * x - g, mu);
+        double bx = rcv[r] * soft_thr(dgv[r] * x - g, tau);
         if constexpr (POS) bx = bx < 0.0 ? 0.0 : bx;   // (a NaN stays a NaN)
         double dprime;
         if constexpr (DS == 2) {
@@ -584,14 +608,19 @@ __device__ __forceinline__ void panel_shrink4(const f32x4& acc, const float (&xs
                 }
             }
         }
-        sbx += fabs(x + dprime);
-        sx += fabs(x);
+        if constexpr (PF) {
+            sbx += pnv[r] * fabs(x + dprime);
+            sx += pnv[r] * fabs(x);
+        } else {
+            sbx += fabs(x + dprime);
+            sx += fabs(x);
+        }
         double e;
         if constexpr (POS) {
-            const double px = x - g - mu;
+            const double px = x - g - tau;
             e = fabs(x - (px > 0.0 ? px : 0.0));
         } else {
-            e = fabs(g - proj(g - x, -mu, mu));
+            e = fabs(g - proj(g - x, -tau, tau));
         }
         err = nan_max(err, e);
     }
@@ -629,7 +658,9 @@ __device__ __forceinline__ void panel_norms_out(const PanelParams& p, const doub
 }
 
 // (BPGL_PANEL_DIAG's epilogue bits: see the macro.)
-template <int NTW, int EPI, int DS, int GM = 0, int NW = 0, bool POS = false>
+// PF: the fused shrink (EPI 1) does not write Gout, and with the penalty factors that argument carries them
+// instead -- p [nblock][w] fp64, the layout of diag -- so that PanelParams stays what it is.
+template <int NTW, int EPI, int DS, int GM = 0, int NW = 0, bool POS = false, bool PF = false>
 __device__ __forceinline__ void panel_pass1_epilogue(const PanelParams& p, int mb, long long c0, int wm, int wn,
                                                      int T, f32x4 (&acc)[4][NTW], char* smem,
                                                      double* __restrict__ Gout) {
@@ -649,6 +680,7 @@ __device__ __forceinline__ void panel_pass1_epilogue(const PanelParams& p, int m
         return;
     }
     double* nred = reinterpret_cast<double*>(smem);   // [4 wm][k][4]
+    const double* pen = Gout;                         // PF only
     if constexpr ((BPGL_PANEL_DIAG & 8) != 0) {
         float sink = 0.f;
 #pragma unroll
@@ -672,9 +704,10 @@ __device__ __forceinline__ void panel_pass1_epilogue(const PanelParams& p, int m
         constexpr int RS = 1024 + 16;                 // LDS row stride (+16 B: conflict-free 16-B reads)
         constexpr int NR = 32;                        // RHS rows per phase
         constexpr int BUF = (GM == 2 ? 2 : 1) * NR * RS;
-        static_assert(2 * 2 * NR * RS + 6144 + 4 * 128 * 4 * 8 <= 160 * 1024, "LDS budget");
+        constexpr int PFB = PF ? 2048 : 0;            // the penalty factors p [256] (fp64), after gamma
+        static_assert(2 * 2 * NR * RS + 6144 + PFB + 4 * 128 * 4 * 8 <= 160 * 1024, "LDS budget");
         char* dgl = smem + 2 * BUF;                   // diag [256], rec [256], mu [128], gamma [128] (fp64)
-        double* nrd = reinterpret_cast<double*>(dgl + 6144);
+        double* nrd = reinterpret_cast<double*>(dgl + 6144 + PFB);
         const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
         __syncthreads();                              // the mainloop's last LDS reads are done
         // every operand by LDS-DMA (vmcnt retires in order: a plain load issued after the next
@@ -684,6 +717,8 @@ __device__ __forceinline__ void panel_pass1_epilogue(const PanelParams& p, int m
                    dgl + wave * 1024);
         else if (wave < 6)
             glds16((wave == 4 ? p.mu : p.gamma) + lane * 2, dgl + 4096 + (wave - 4) * 1024);
+        else if constexpr (PF)   // waves 6 and 7: issued before their first phase's DMA, so it retires first
+            glds16(pen + (long long)mb * p.w + c0 + (wave & 1) * 128 + lane * 2, dgl + 6144 + (wave - 6) * 1024);
         auto issue = [&](int nt, char* buf) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -726,10 +761,27 @@ __device__ __forceinline__ void panel_pass1_epilogue(const PanelParams& p, int m
             for (int mt = 0; mt < 4; ++mt) {
                 const int cc = wm * 64 + mt * 16 + (lane >> 4) * 4;   // column within the block
                 const long long j = c0 + cc;
-                u32x4 vx = lds_rd128(lds_off(buf + rl * RS + cc * 4)), vg = {0u, 0u, 0u, 0u};
-                if constexpr (GM == 2) vg = lds_rd128(lds_off(buf + (NR + rl) * RS + cc * 4));
-                u32x4 vd0 = lds_rd128(lds_off(dgl + cc * 8)), vd1 = lds_rd128(lds_off(dgl + cc * 8 + 16));
-                u32x4 vr0 = lds_rd128(lds_off(dgl + 2048 + cc * 8)), vr1 = lds_rd128(lds_off(dgl + 2048 + cc * 8 + 16));
+                u32x4 vx = {0u, 0u, 0u, 0u}, vg = {0u, 0u, 0u, 0u}, vd0 = vx, vd1 = vx, vr0 = vx, vr1 = vx;
+                if constexpr (!PF) {
+                    vx = lds_rd128(lds_off(buf + rl * RS + cc * 4));
+                    if constexpr (GM == 2) vg = lds_rd128(lds_off(buf + (NR + rl) * RS + cc * 4));
+                    vd0 = lds_rd128(lds_off(dgl + cc * 8)), vd1 = lds_rd128(lds_off(dgl + cc * 8 + 16));
+                    vr0 = lds_rd128(lds_off(dgl + 2048 + cc * 8)), vr1 = lds_rd128(lds_off(dgl + 2048 + cc * 8 + 16));
+                }
+                u32x4 vp0 = {0u, 0u, 0u, 0u}, vp1 = {0u, 0u, 0u, 0u};
+                if constexpr (PF) {
+                    // the PF forms have no registers to spare: every read of the step through two
+                    // address registers (the RHS row's and the staged vectors') and offsets in the instructions
+                    const int c0w = wm * 64 + (lane >> 4) * 4;     // cc at mt = 0
+                    const unsigned xa = lds_off(buf + rl * RS + c0w * 4), da = lds_off(dgl + c0w * 8);
+                    vx = lds_rd128q<64, 0>(xa, mt);
+                    if constexpr (GM == 2) vg = lds_rd128q<64, NR * RS>(xa, mt);
+                    vd0 = lds_rd128q<128, 0>(da, mt);
+                    vd1 = lds_rd128q<128, 16>(da, mt);
+                    vr0 = lds_rd128q<128, 2048>(da, mt);
+                    vr1 = lds_rd128q<128, 2048 + 16>(da, mt);
+                    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(vx), "+v"(vg), "+v"(vd0), "+v"(vd1), "+v"(vr0), "+v"(vr1));
+                } else
                 asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(vx), "+v"(vg), "+v"(vd0), "+v"(vd1), "+v"(vr0), "+v"(vr1));
                 const float4 x4 = __builtin_bit_cast(float4, vx);
                 float gs[4] = {0.f, 0.f, 0.f, 0.f};
@@ -754,7 +806,15 @@ __device__ __forceinline__ void panel_pass1_epilogue(const PanelParams& p, int m
                         put(p.X, ((long long)mb * p.k + rhs) * p.w + j, make_float4(xs[0], xs[1], xs[2], xs[3]));
                 }
                 __bf16 dh[4], dl[4];
-                panel_shrink4<DS, GM, POS>(acc[mt][nt], xs, gs, dgv, rcv, mu, dh, dl, sbx, sx, err);
+                if constexpr (PF) {   // p only now, after the deferred x update: eight registers fewer while that runs
+                    const unsigned da = lds_off(dgl + (wm * 64 + (lane >> 4) * 4) * 8);
+                    vp0 = lds_rd128q<128, 6144>(da, mt);
+                    vp1 = lds_rd128q<128, 6144 + 16>(da, mt);
+                    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(vp0), "+v"(vp1));
+                }
+                const double2 p01 = __builtin_bit_cast(double2, vp0), p23 = __builtin_bit_cast(double2, vp1);
+                const double pnv[4] = {p01.x, p01.y, p23.x, p23.y};
+                panel_shrink4<DS, GM, POS, PF>(acc[mt][nt], xs, gs, dgv, rcv, mu, dh, dl, sbx, sx, err, pnv);
                 if constexpr (GM != 0)   // read again only next iteration, after all of A: non-temporal
                     __builtin_nontemporal_store(f32x4{gs[0], gs[1], gs[2], gs[3]},
                                                 reinterpret_cast<f32x4*>(p.Gc + (long long)rhs * p.w + j));
@@ -802,8 +862,10 @@ __device__ __forceinline__ void panel_pass1_epilogue(const PanelParams& p, int m
         b = *reinterpret_cast<const double2*>(base + kx + 2);
     };
     double2 dq01, dq23, rq01, rq23;
+    double2 pq01 = {1.0, 1.0}, pq23 = {1.0, 1.0};   // PF: the lane's p, loaded where diag and rec are
     lddr(p.diag, 0, dq01, dq23);
     lddr(p.rec, 0, rq01, rq23);
+    if constexpr (PF) lddr(pen, 0, pq01, pq23);
     float4 xq = *reinterpret_cast<const float4*>(xptr(0, 0));
     float4 gq = make_float4(0.f, 0.f, 0.f, 0.f);
     if constexpr (GM == 2) gq = *reinterpret_cast<const float4*>(gptr(0, 0));
@@ -823,11 +885,12 @@ __device__ __forceinline__ void panel_pass1_epilogue(const PanelParams& p, int m
             const int q1 = nt * 4 + mt + 1, nt1 = q1 / 4, mt1 = q1 % 4;
             float4 xn = xq, gn = gq;
             bf16x4 hn1 = hq1;
-            double2 dn01 = dq01, dn23 = dq23, rn01 = rq01, rn23 = rq23;
+            double2 dn01 = dq01, dn23 = dq23, rn01 = rq01, rn23 = rq23, pn01 = pq01, pn23 = pq23;
             if (q1 < NTW * 4) {
                 if constexpr (DS == 1) {   // (with the hi + lo direction the registers are not there: no spills)
                     lddr(p.diag, mt1, dn01, dn23);
                     lddr(p.rec, mt1, rn01, rn23);
+                    if constexpr (PF) lddr(pen, mt1, pn01, pn23);
                 }
                 xn = *reinterpret_cast<const float4*>(xptr(nt1, mt1));
                 if constexpr (GM == 2) gn = *reinterpret_cast<const float4*>(gptr(nt1, mt1));
@@ -847,12 +910,14 @@ __device__ __forceinline__ void panel_pass1_epilogue(const PanelParams& p, int m
                 if (q1 > 1) {   // step 0's came with the prologue
                     lddr(p.diag, mt, dq01, dq23);
                     lddr(p.rec, mt, rq01, rq23);
+                    if constexpr (PF) lddr(pen, mt, pq01, pq23);
                 }
             }
             float gs[4] = {gq.x, gq.y, gq.z, gq.w};
             const double dgv[4] = {dq01.x, dq01.y, dq23.x, dq23.y};
             const double rcv[4] = {rq01.x, rq01.y, rq23.x, rq23.y};
-            panel_shrink4<DS, GM, POS>(acc[mt][nt], xs, gs, dgv, rcv, mu, dh, dl, sbx, sx, err);
+            const double pnv[4] = {pq01.x, pq01.y, pq23.x, pq23.y};
+            panel_shrink4<DS, GM, POS, PF>(acc[mt][nt], xs, gs, dgv, rcv, mu, dh, dl, sbx, sx, err, pnv);
             if constexpr (GM != 0 && (BPGL_PANEL_DIAG & 1) == 0)
                 *reinterpret_cast<float4*>(p.Gc + (long long)rhs * p.w + j) = make_float4(gs[0], gs[1], gs[2], gs[3]);
             if constexpr ((BPGL_PANEL_DIAG & 2) == 0)
@@ -861,6 +926,7 @@ __device__ __forceinline__ void panel_pass1_epilogue(const PanelParams& p, int m
                 put(p.Dl, (long long)rhs * p.ldd + j, bf16x4{dl[0], dl[1], dl[2], dl[3]});
             xq = xn; gq = gn; hq1 = hn1;
             dq01 = dn01; dq23 = dn23; rq01 = rn01; rq23 = rn23;
+            if constexpr (PF) { pq01 = pn01; pq23 = pn23; }
         }
         panel_norms_wave(nred, wm, K, rhs, sbx, sx, err);
     }
@@ -872,8 +938,9 @@ __device__ __forceinline__ void panel_pass1_epilogue(const PanelParams& p, int m
 // pass 1: G = A_m^T R (EPI 0: write G [k][w] fp64 -- API), or the fused shrink
 // epilogue (EPI 1: the direction D' in DS bf16 pieces (2: Dh + Dl, 1: Dh alone), norms
 // per RHS).  grid = w / 256 blocks.  R always enters as hi + lo.  POS: the non-negative shrink (panel_shrink4).
+// PF: the penalty factors' shrink; Gout is then the factors p [nblock][w] (panel_pass1_epilogue).
 // ---------------------------------------------------------------------------
-template <int NT, int EPI, int ILV, int DS, int GM = 0, bool POS = false>
+template <int NT, int EPI, int ILV, int DS, int GM = 0, bool POS = false, bool PF = false>
 __global__ __launch_bounds__((PanelGeo<NT, 2>::T)) void k_panel_pass1(PanelParams p, int fixed_block,
                                                                          double* __restrict__ Gout) {
     using G = PanelGeo<NT, 2>;
@@ -890,7 +957,7 @@ __global__ __launch_bounds__((PanelGeo<NT, 2>::T)) void k_panel_pass1(PanelParam
     else
         panel_gemm<NT, 1, ILV, 2>(smem, p.A1t, ld1, 0, (long long)mb * p.w + c0, p.Rh, p.Rl, p.ldr, 0,
                                   (int)(p.m / kPanelK), acc);
-    panel_pass1_epilogue<G::NTW, EPI, DS, GM, G::NW, POS>(p, mb, c0, wm, wn, G::T, acc, smem, Gout);
+    panel_pass1_epilogue<G::NTW, EPI, DS, GM, G::NW, POS, PF>(p, mb, c0, wm, wn, G::T, acc, smem, Gout);
 }
 
 // ---------------------------------------------------------------------------

@@ -15,6 +15,7 @@
 #include "bpgl_panel.h"
 #include "bpgl_panel_gap.h"
 #include "bpgl_panel_pos.h"
+#include "bpgl_panel_pen.h"
 
 using namespace bpgl;
 using namespace bpgl_host;
@@ -27,7 +28,7 @@ constexpr int kPanelKinds = 5;   // pass1, pass2, reduce, step, update
 // byte offsets of the scratch regions (panel_layout), in the order they are laid out
 struct PanelLayout {
     int64_t st, Rh, Rl, Dh, Dl, X, Ax, B, R, diag, rec, Sslab, S, norms, lsp, mu, gamma, err_rhs, cnt, ready, lsdone, Gc,
-        Sh, Ec, At, A1t, gpart, gparts, gcounts, gres, W, Bh, ghold, lss, cshift, nw, bmean, gipart, gicp, total;
+        Sh, Ec, At, A1t, gpart, gparts, gcounts, gres, W, Bh, ghold, lss, cshift, nw, bmean, gipart, gicp, pen, total;
 };
 
 struct bpgl_panel {
@@ -59,6 +60,7 @@ struct bpgl_panel {
     bool user_mask = false;       // ... and it is the caller's (bpgl_panel_set_row_mask)
     bool icpt = false;            // bpgl_panel_set_intercept: the intercept (IC) kernel variants run (always with `masked`)
     bool positive = false;        // bpgl_panel_set_positive: x >= 0 (the POS pass-1 variants, the one-sided certificate)
+    bool penalty = false;         // bpgl_panel_set_penalty: per-column l1 weights (the PF pass-1 variants, the weighted certificate)
     bool icpt_valid = false;      // a bpgl_panel_gap has run since the last reset: icpt_host is its beta0
     std::vector<double> icpt_host;
     char* scratch = nullptr;      // the caller's scratch and its layout (bpgl_panel_bind)
@@ -161,6 +163,9 @@ PanelLayout panel_layout(const bpgl_panel* c) {
     L.bmean = k.take(8 * (int64_t)c->k);
     L.gipart = k.take(8 * (km / kThreads));
     L.gicp = k.take(8 * 2 * (int64_t)c->k);
+    // the penalty factors (bpgl_panel_set_penalty): p [n] fp64 and, behind them, the validation kernel's flag.
+    // After everything else once more.
+    L.pen = k.take(8 * c->n + 256);
     L.total = k.off;
     return L;
 }
@@ -190,8 +195,14 @@ int panel_launch(bpgl_panel* c, int which, int fixed_block, double* out, int mod
                         });
                     if (mode && c->positive)   // the POS variant of the same form, from its own code object
                         pass1 = bpgl_pos::pass1(c->k, ILV, NS, c->gm_cur);
+                    double* arg3 = out;
+                    if (mode && c->penalty) {   // the PF variants: the factors travel where the API product's G does
+                        pass1 = c->positive ? bpgl_pen::pass1_pos(c->k, ILV, NS, c->gm_cur)
+                                            : bpgl_pen::pass1(c->k, ILV, NS, c->gm_cur);
+                        arg3 = c->at<double>(c->L.pen);
+                    }
                     hipLaunchKernelGGL(pass1, dim3((unsigned)(c->w / kPanelRows)), dim3(PanelGeo<NT, 2>::T), 0,
-                                       c->stream, c->p, fixed_block, out);
+                                       c->stream, c->p, fixed_block, arg3);
                     LAUNCH_CHECK("k_panel_pass1");
                 } else {
                     hipLaunchKernelGGL((k_panel_pass2<NT, ILV, NS>), dim3((unsigned)((c->m / kPanelRows) * c->kchunks)),
@@ -518,7 +529,7 @@ int bpgl_panel_bind(bpgl_panel* c, const void* A, int64_t lda, void* scratch, in
     hipLaunchKernelGGL((k_panel_tile<64, 256, false>), dim3((unsigned)((c->m / 64) * (c->n / 256))), dim3(256), 0,
                        c->stream, p.A, p.lda, c->n, c->at<__bf16>(L.A1t));
     LAUNCH_CHECK("k_panel_tile");
-    c->masked = c->user_mask = c->icpt = c->icpt_valid = c->positive = false;   // p.W is null again
+    c->masked = c->user_mask = c->icpt = c->icpt_valid = c->positive = c->penalty = false;   // p.W is null again
     panel_fuse_check(c);
     c->bound = true;
     c->have_diag = false;
@@ -761,6 +772,7 @@ int bpgl_panel_get_tuning(const bpgl_panel* c, const char* key, int64_t* value) 
     else if (!strcmp(key, "carry_g")) *value = panel_carry(c) ? 1 : 0;   // the form in effect
     else if (!strcmp(key, "g_refresh")) *value = c->g_period;
     else if (!strcmp(key, "positive")) *value = c->positive ? 1 : 0;   // bpgl_panel_set_positive
+    else if (!strcmp(key, "penalty")) *value = c->penalty ? 1 : 0;     // bpgl_panel_set_penalty
     else return fail(BPGL_E_ARG, "unknown panel tuning key '%s'", key);
     return 0;
 }
@@ -803,6 +815,33 @@ int bpgl_panel_set_positive(bpgl_panel* c, int on) {
     if ((rc = panel_ready(c))) return rc;
     c->positive = on != 0;
     c->solver = false;   // the graphs bake the pass-1 variant in: a reset must follow
+    drop_graphs(c);
+    return 0;
+}
+
+int bpgl_panel_set_penalty(bpgl_panel* c, const double* pen) {
+    int rc;
+    if ((rc = panel_ready(c))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (pen) {
+        // validated where the caller has it, so that a refused vector leaves the installed one in force
+        double* dst = c->at<double>(c->L.pen);
+        int* flag = reinterpret_cast<int*>(dst + c->n);
+        int bad = 0;
+        HIP_TRY(hipMemsetAsync(flag, 0, sizeof(int), c->stream));
+        hipLaunchKernelGGL(bpgl_pen::check(), dim3((unsigned)std::min<int64_t>(cdiv(c->n, kThreads), 2048)), dim3(kThreads),
+                           0, c->stream, pen, (long long)c->n, flag);
+        LAUNCH_CHECK("k_panel_check_pen");
+        HIP_TRY(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (bad) return fail(BPGL_E_ARG, "every penalty factor must be finite and > 0");
+        if (pen != dst) {   // a set-up call: done when it returns, so the caller's buffer is free
+            HIP_TRY(hipMemcpyAsync(dst, pen, 8 * c->n, hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+        }
+    }
+    c->penalty = pen != nullptr;
+    c->solver = false;   // the graphs bake the pass-1 variant and its argument in: a reset must follow
     drop_graphs(c);
     return 0;
 }
@@ -850,6 +889,11 @@ int bpgl_panel_gap(bpgl_panel* c, double* G_all, double* R_fresh, uint8_t* keep,
         HIP_TRY(hipEventRecord(c->gap_ev[prod], c->stream));
     }
     const int nparts = pgap_nparts(c);
+    const double* pen = c->at<double>(L.pen);
+    if (c->penalty)
+        hipLaunchKernelGGL(c->positive ? bpgl_pen::gap_partials_pos() : bpgl_pen::gap_partials(),
+                           dim3((unsigned)nparts, (unsigned)c->k), dim3(kThreads), 0, c->stream, a, parts, pen);
+    else
     hipLaunchKernelGGL(c->positive ? bpgl_pos::gap_partials() : &k_pgap_partials<false>,
                        dim3((unsigned)nparts, (unsigned)c->k), dim3(kThreads), 0, c->stream, a, parts);
     LAUNCH_CHECK("k_pgap_partials");
@@ -862,6 +906,10 @@ int bpgl_panel_gap(bpgl_panel* c, double* G_all, double* R_fresh, uint8_t* keep,
     }
     if (keep) {
         const int64_t nb = cdiv(c->n, kThreads);
+        if (c->penalty)
+            hipLaunchKernelGGL(c->positive ? bpgl_pen::gap_screen_pos() : bpgl_pen::gap_screen(),
+                               dim3((unsigned)nb, (unsigned)c->k), dim3(kThreads), 0, c->stream, a, res, keep, counts, pen);
+        else
         hipLaunchKernelGGL(c->positive ? bpgl_pos::gap_screen() : &k_pgap_screen<false>,
                            dim3((unsigned)nb, (unsigned)c->k), dim3(kThreads), 0, c->stream, a, res, keep, counts);
         LAUNCH_CHECK("k_pgap_screen");

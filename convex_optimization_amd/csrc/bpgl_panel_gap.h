@@ -39,6 +39,12 @@
 //   k_pgap_partials         max |g| becomes max_j (-g_j)+, so scale = min(1, mu / that) makes scale r feasible for the
 //                           one-sided dual constraint -a_j . theta <= mu; primal, dual and gap keep their formulas
 //   k_pgap_screen           score_j = scale (-g_j) + sqrt(d_j) sqrt(2 max(gap, 0))
+// With penalty factors p (bpgl_panel_set_penalty; k_pgap_partials_pf and k_pgap_screen_pf,
+// the same bodies with one more argument, which only bpgl_panel_pen.hip instantiates):
+//   k_pgap_partials_pf      sum |x| becomes sum p_j |x_j| and max |g| becomes max_j |g_j| / p_j (max_j (-g_j)+ / p_j
+//                           with POS), so scale = min(1, mu / that) gives |a_j . (scale r)| <= mu p_j; k_pgap_final is
+//                           unchanged
+//   k_pgap_screen_pf        keep_j = not (score_j < mu p_j), the score as above
 // Every reduction walks its dimension in a fixed order (within a chunk: 32-deep stages in index
 // order, 4 at a time through the MFMA; then the chunks; then wave_sum / wave_max, the waves, the
 // blocks in index order).  No floating-point atomics: two calls on the same state return the same
@@ -335,8 +341,9 @@ __global__ __launch_bounds__(kThreads) void k_pgap_holdout(const double* __restr
 
 // grid (nparts, k); parts[k][nparts][kPgPart].  POS: the dual constraint is one-sided, -a_j . theta <= mu, and
 // the fourth partial is max (-g)+ instead of max |g|
-template <bool POS = false>
-__global__ __launch_bounds__(kThreads) void k_pgap_partials(PanelGapArgs a, double* __restrict__ parts) {
+template <bool POS, bool PF>
+__device__ __forceinline__ void pgap_partials_body(const PanelGapArgs& a, double* __restrict__ parts,
+                                                   const double* __restrict__ pen) {
     const int k = blockIdx.y;
     const long long tid = (long long)blockIdx.x * kThreads + threadIdx.x;
     const long long stride = (long long)gridDim.x * kThreads;
@@ -352,12 +359,18 @@ __global__ __launch_bounds__(kThreads) void k_pgap_partials(PanelGapArgs a, doub
     }
     for (long long j = tid; j < a.n; j += stride) {
         const long long e = ((j / a.w) * a.k + k) * a.w + j % a.w;
+        if constexpr (PF) {   // the weighted l1 norm and the weighted dual norm (p_j > 0 and finite: set_penalty)
+            const double pj = pen[j], gv = a.G[e];
+            ax += pj * fabs((double)a.X[e]);
+            gm = nan_max(gm, (POS ? (gv > 0.0 ? 0.0 : -gv) : fabs(gv)) / pj);
+        } else {
         ax += fabs((double)a.X[e]);
         if constexpr (POS) {
             const double gv = a.G[e];
             gm = nan_max(gm, gv > 0.0 ? 0.0 : -gv);   // (a NaN stays a NaN)
         } else {
             gm = nan_max(gm, fabs(a.G[e]));
+        }
         }
     }
     rr = wave_sum(rr);
@@ -375,6 +388,16 @@ __global__ __launch_bounds__(kThreads) void k_pgap_partials(PanelGapArgs a, doub
         for (int q = 3; q < 5; ++q)
             dst[q] = nan_max(nan_max(nan_max(red[q][0], red[q][1]), red[q][2]), red[q][3]);
     }
+}
+template <bool POS = false>
+__global__ __launch_bounds__(kThreads) void k_pgap_partials(PanelGapArgs a, double* __restrict__ parts) {
+    pgap_partials_body<POS, false>(a, parts, nullptr);
+}
+// ... with the penalty factors pen [n], global column order
+template <bool POS>
+__global__ __launch_bounds__(kThreads) void k_pgap_partials_pf(PanelGapArgs a, double* __restrict__ parts,
+                                                               const double* __restrict__ pen) {
+    pgap_partials_body<POS, true>(a, parts, pen);
 }
 
 #ifndef BPGL_PANEL_TEMPLATES_ONLY
@@ -425,10 +448,11 @@ __global__ __launch_bounds__(kThreads) void k_pgap_final(const double* __restric
 
 // grid (ceil(n / kThreads), k): keep[k][j] for the global column j; counts[k][block] = columns kept.
 // POS: score_j = scale (-g_j) + ...
-template <bool POS = false>
-__global__ __launch_bounds__(kThreads) void k_pgap_screen(PanelGapArgs a, const double* __restrict__ res_all,
-                                                          unsigned char* __restrict__ keep,
-                                                          int* __restrict__ counts) {
+// (the body's pointers carry no __restrict__: the kernels' own qualifiers say it already, and a second set changed
+// the instruction schedule of the instantiations that existed)
+template <bool POS, bool PF>
+__device__ __forceinline__ void pgap_screen_body(const PanelGapArgs& a, const double* res_all, unsigned char* keep,
+                                                 int* counts, const double* pen) {
     const int k = blockIdx.y;
     const long long j = (long long)blockIdx.x * kThreads + threadIdx.x;
     bool kp = false;
@@ -438,7 +462,8 @@ __global__ __launch_bounds__(kThreads) void k_pgap_screen(PanelGapArgs a, const 
         const double gp = gap < 0.0 ? 0.0 : gap;   // a NaN stays a NaN
         const double g = a.G[((j / a.w) * a.k + k) * a.w + j % a.w];
         const double score = s * (POS ? -g : fabs(g)) + sqrt(a.diag[j]) * sqrt(2.0 * gp);
-        kp = !(score < a.mu[k]);
+        if constexpr (PF) kp = !(score < a.mu[k] * pen[j]);
+        else kp = !(score < a.mu[k]);
         keep[(long long)k * a.n + j] = kp ? 1 : 0;
     }
     const int cnt = __popcll(__ballot(kp));
@@ -447,6 +472,19 @@ __global__ __launch_bounds__(kThreads) void k_pgap_screen(PanelGapArgs a, const 
     if (lane == 0) red[wave] = cnt;
     __syncthreads();
     if (threadIdx.x == 0) counts[(long long)k * gridDim.x + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+template <bool POS = false>
+__global__ __launch_bounds__(kThreads) void k_pgap_screen(PanelGapArgs a, const double* __restrict__ res_all,
+                                                          unsigned char* __restrict__ keep,
+                                                          int* __restrict__ counts) {
+    pgap_screen_body<POS, false>(a, res_all, keep, counts, nullptr);
+}
+template <bool POS>
+__global__ __launch_bounds__(kThreads) void k_pgap_screen_pf(PanelGapArgs a, const double* __restrict__ res_all,
+                                                             unsigned char* __restrict__ keep,
+                                                             int* __restrict__ counts,
+                                                             const double* __restrict__ pen) {
+    pgap_screen_body<POS, true>(a, res_all, keep, counts, pen);
 }
 
 #ifndef BPGL_PANEL_TEMPLATES_ONLY

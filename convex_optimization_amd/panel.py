@@ -41,6 +41,9 @@ right-hand side's own in-rows inside the fold, and ``lasso_path`` / ``lasso_cv``
 ``PanelLasso.set_positive`` adds the sign constraint x >= 0 (scikit-learn's ``positive=True``, glmnet's
 ``lower.limits = 0``) to every right-hand side -- every stored iterate is then >= 0 -- and ``lasso_path`` /
 ``lasso_cv`` take ``positive``.
+``PanelLasso.set_penalty_factors`` gives column j the l1 weight p_j > 0 (glmnet's ``penalty.factor``, the adaptive
+lasso's weights; used as given, not renormalised), one vector for all right-hand sides on the A that is bound,
+and ``lasso_path`` / ``lasso_cv`` take ``penalty_factors``.
 
 All compute goes through libbpgl.so (bpgl_panel_* in include/bpgl.h).
 """
@@ -82,6 +85,7 @@ _PANEL_SIGS = {
     "bpgl_panel_set_intercept": (ctypes.c_int, [_p, ctypes.c_int]),
     "bpgl_panel_intercept": (ctypes.c_int, [_p, ctypes.POINTER(ctypes.c_double)]),
     "bpgl_panel_set_positive": (ctypes.c_int, [_p, ctypes.c_int]),
+    "bpgl_panel_set_penalty": (ctypes.c_int, [_p, _p]),
 }
 N._SIGS.update(_PANEL_SIGS)
 
@@ -286,6 +290,20 @@ class PanelLasso:
         one-sided), and ``set_positive(False)`` restores the plain solver bitwise."""
         N.check(_lib().bpgl_panel_set_positive(self._ctx, int(bool(on))), "bpgl_panel_set_positive")
 
+    def set_penalty_factors(self, p):
+        """Per-column l1 weights (bpgl_panel_set_penalty): every right-hand side minimises
+        1/2 ||w o (A x - b)||^2 + mu sum_j p_j |x_j| (with the row mask, the intercept and x >= 0 when those are
+        on).  ``p``: a numpy array or torch tensor of length n, every entry finite and > 0 (ValueError otherwise,
+        before any device work), or None to switch it off.  The factors are used as given -- no renormalisation
+        to sum p = n as glmnet applies.  A ``solver_reset`` must follow.  ``duality_gap`` then certifies the
+        weighted problem: gnorm_inf is max_j |g_j| / p_j (at x = 0: mu_max) and the screen compares with mu p_j.
+        A vector of ones, and ``set_penalty_factors(None)``, give the plain solver bitwise."""
+        pen = _check_penalty(p, self.MAT_WIDTH_ALL)
+        with self._on_stream():
+            self._pen = None if pen is None else torch.from_numpy(pen).to(self.device)
+            N.check(_lib().bpgl_panel_set_penalty(self._ctx, N.ptr(self._pen)), "bpgl_panel_set_penalty")
+        self.stream.synchronize()
+
     def solver_step(self, n_iter):
         with self._on_stream():
             N.check(_lib().bpgl_panel_step(self._ctx, int(n_iter)), "bpgl_panel_step")
@@ -432,6 +450,20 @@ def _check_loop(pl, target, ITER_MAX, check_every):
     return t, cert, first
 
 
+def _check_penalty(p, n):
+    """``p`` as a contiguous fp64 numpy vector of length ``n``, every entry finite and > 0 (ValueError otherwise);
+    None stays None.  Needs no GPU."""
+    if p is None:
+        return None
+    pen = np.array(p.detach().cpu().numpy() if isinstance(p, torch.Tensor) else p, dtype=np.float64)   # a copy
+    if pen.ndim != 1 or pen.size != int(n):
+        raise ValueError(f"penalty factors must be a vector of length n = {int(n)}, got shape {pen.shape}")
+    if not np.all(np.isfinite(pen) & (pen > 0.0)):
+        raise ValueError("every penalty factor must be finite and > 0 (an unpenalised or an excluded column is "
+                         "not a penalty factor: DESIGN.md section 15)")
+    return pen
+
+
 def _check_shrink(shrink):
     if not 0.0 <= float(shrink) < 1.0:
         raise ValueError("shrink must lie in [0, 1)")
@@ -450,7 +482,8 @@ def _grid_below(mu_max, n_mus, hi, lo, positive):
     return mu_grid(float(mu_max), n_mus, hi, lo)
 
 
-def _screened_loop(pl, B, mu, target, ITER_MAX, check_every, shrink, mask=None, intercept=False, positive=False):
+def _screened_loop(pl, B, mu, target, ITER_MAX, check_every, shrink, mask=None, intercept=False, positive=False,
+                   penalty=None):
     """``_check_loop`` on a freshly reset ``pl`` (reset with ``B``, ``mu``; ``mask``: the (m, k) row mask
     installed on it, or None) with gap-safe compaction, ``ClassLassoScreened``'s rule on a panel: after
     a check that did not stop the loop, the union over the panel's columns of the screen's keep goes
@@ -459,6 +492,8 @@ def _screened_loop(pl, B, mu, target, ITER_MAX, check_every, shrink, mask=None, 
     the same Block and width is built over them, the mask (and, with ``intercept`` / ``positive``, the
     intercept / the sign constraint, which ``pl`` then has on too) installed there, and the solve continues
     from ``solver_reset(B, mu, x0=X[sel])``.  ``pl`` stays alive; an earlier narrow context is dropped.
+    ``penalty``: the (n,) penalty factors installed on ``pl`` (or None); a narrower context gets them gathered with
+    the same columns.
 
     Returns dict(t, cert, first, reached, x (n, k), active, compactions [(t, n_active after)],
     compact_seconds).  ``reached`` is the loop's own verdict.  After a compaction ``cert`` is one
@@ -494,6 +529,8 @@ def _screened_loop(pl, B, mu, target, ITER_MAX, check_every, shrink, mask=None, 
                 nxt.set_intercept(True)
             if positive:
                 nxt.set_positive(True)
+            if penalty is not None:
+                nxt.set_penalty_factors(penalty[active[sel]])
             if mask is not None:
                 nxt.set_row_mask(mask)
             nxt.solver_reset(B, mu, x0=x0)
@@ -517,7 +554,8 @@ def _screened_loop(pl, B, mu, target, ITER_MAX, check_every, shrink, mask=None, 
 
 
 def lasso_path(A, b, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_BOUND=1e-4, ITER_MAX=4096,
-               check_every=PATH_CHECK_EVERY, device=None, x0=None, shrink=0.0, fit_intercept=False, positive=False):
+               check_every=PATH_CHECK_EVERY, device=None, x0=None, shrink=0.0, fit_intercept=False, positive=False,
+               penalty_factors=None):
     """A regularization path as ONE panel: min 1/2 ||A x - b||^2 + mu ||x||_1 for every mu of a grid,
     on the bf16-stored A, every column of the panel holding the same b.
 
@@ -551,7 +589,13 @@ def lasso_path(A, b, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_BOUND=1e-4
     ``positive``: every mu solves the problem subject to x >= 0
     (``PanelLasso.set_positive``, also on every narrower context of ``shrink``); the returned x is >= 0
     elementwise, an ``x0`` is projected to max(x0, 0), and with ``mus=None`` mu_max is max_j (a_j . b)+
-    (ValueError when that is 0: no column correlates positively with b)."""
+    (ValueError when that is 0: no column correlates positively with b).
+
+    ``penalty_factors``: an (n,) vector p, every entry finite and > 0 (ValueError
+    otherwise); every mu solves min 1/2 ||A x - b||^2 + mu sum_j p_j |x_j| (``PanelLasso.set_penalty_factors``,
+    on every narrower context of ``shrink`` gathered with its columns).  Used as given, not renormalised.  With
+    ``mus=None`` mu_max is max_j |a_j . b| / p_j."""
+    penalty = _check_penalty(penalty_factors, int(A.shape[1]))
     if int(check_every) <= 0:
         raise ValueError("check_every must be > 0")
     shrink = _check_shrink(shrink)
@@ -578,6 +622,8 @@ def lasso_path(A, b, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_BOUND=1e-4
         pl.set_intercept(True)
     if positive:
         pl.set_positive(True)
+    if penalty is not None:
+        pl.set_penalty_factors(penalty)
     B = np.repeat(b[:, None], k, axis=1)
     mu_max = None
     if grid is None:
@@ -592,7 +638,7 @@ def lasso_path(A, b, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_BOUND=1e-4
     bc = b - b.mean() if fit_intercept else b
     target = float(GAP_BOUND) * 0.5 * float(bc @ bc)
     run = _screened_loop(pl, B, grid, target, ITER_MAX, check_every, shrink, intercept=bool(fit_intercept),
-                         positive=bool(positive))
+                         positive=bool(positive), penalty=penalty)
     cert = run["cert"]
     out = dict(x=run["x"][:, :n_given], mus=grid[:n_given].copy(), mu_max=mu_max, iters=run["t"],
                reached=run["reached"][:n_given], first_reached=run["first"][:n_given])
@@ -605,7 +651,7 @@ def lasso_path(A, b, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_BOUND=1e-4
 
 def lasso_cv(A, b, n_folds=8, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_BOUND=1e-4, ITER_MAX=4096,
              check_every=PATH_CHECK_EVERY, seed=0, masks=None, refit=True, return_x=False, device=None,
-             shrink=0.0, warm_refit=False, fit_intercept=False, positive=False):
+             shrink=0.0, warm_refit=False, fit_intercept=False, positive=False, penalty_factors=None):
     """K-fold cross-validation over a grid of mu as ONE panel on one bound A: column c = f * n_mus + j
     solves fold f (the rows of ``masks[f]``) at ``mus[j]``, min 1/2 ||w_f o (A x - b)||^2 + mu_j ||x||_1,
     through ``PanelLasso.set_row_mask``.  n_folds * n_mus <= 128 and n_folds >= 2 (ValueError
@@ -644,8 +690,14 @@ def lasso_cv(A, b, n_folds=8, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_B
     ``positive``: every column solves its fold subject to x >= 0
     (``PanelLasso.set_positive``); the refit and every narrower context of ``shrink`` get it too, the
     ``warm_refit`` start (a mean of non-negative solutions) is non-negative, and with ``mus=None`` mu_max is
-    max_j (a_j . b)+ (ValueError when that is 0)."""
+    max_j (a_j . b)+ (ValueError when that is 0).
+
+    ``penalty_factors``: an (n,) vector p, every entry finite and > 0 (ValueError
+    otherwise), shared by every fold: each column solves its fold with the penalty mu sum_j p_j |x_j|
+    (``PanelLasso.set_penalty_factors``); the refit and every narrower context of ``shrink`` get it too.  Used as
+    given, not renormalised.  With ``mus=None`` mu_max is max_j |a_j . b| / p_j."""
     from .cpu_calculation import kfold_masks
+    penalty = _check_penalty(penalty_factors, int(A.shape[1]))
     if int(check_every) <= 0:
         raise ValueError("check_every must be > 0")
     shrink = _check_shrink(shrink)
@@ -678,6 +730,8 @@ def lasso_cv(A, b, n_folds=8, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_B
     positive = bool(positive)
     if positive:
         pl.set_positive(True)
+    if penalty is not None:
+        pl.set_penalty_factors(penalty)
     B = np.repeat(b[:, None], k, axis=1)
     if mus is None:
         pl.solver_reset(B, 1.0)
@@ -691,7 +745,7 @@ def lasso_cv(A, b, n_folds=8, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_B
     bb = np.array([float(centred(masks[f].astype(np.float64), b) @ centred(masks[f].astype(np.float64), b))
                    for f in range(n_folds)])
     run = _screened_loop(pl, B, mus[jmu], float(GAP_BOUND) * 0.5 * bb[fold], ITER_MAX, check_every, shrink,
-                         mask=masks[fold].T, intercept=fit_intercept, positive=positive)
+                         mask=masks[fold].T, intercept=fit_intercept, positive=positive, penalty=penalty)
     t, cert = run["t"], run["cert"]
     shape = (n_folds, n_mus)
     count = (masks == 0).sum(axis=1).astype(np.float64)
@@ -720,7 +774,7 @@ def lasso_cv(A, b, n_folds=8, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_B
             pl.solver_reset(B, grid)
         bc = b - b.mean() if fit_intercept else b
         rrun = _screened_loop(pl, B, grid, float(GAP_BOUND) * 0.5 * float(bc @ bc), ITER_MAX, check_every, shrink,
-                              intercept=fit_intercept, positive=positive)
+                              intercept=fit_intercept, positive=positive, penalty=penalty)
         out.update(x=rrun["x"][:, :n_mus], refit_gap=rrun["cert"]["gap"][:n_mus], refit_iters=rrun["t"],
                    refit_compactions=rrun["compactions"])
         if fit_intercept:

@@ -95,7 +95,13 @@ const char* bpgl_last_error(void);
  *                prox, a feasible bf16 direction image, the one-sided certificate and screen; DESIGN.md
  *                section 14) and the panel tuning key "positive" (bpgl_panel_get_tuning only).  Opt-in:
  *                with it off every kernel that existed is unchanged, bit for bit.
- *                bpgl_panel_scratch_bytes does not change. */
+ *                bpgl_panel_scratch_bytes does not change.
+ *   309 (0.3.9): + bpgl_panel_set_penalty (per-column l1 weights p_j > 0, glmnet's penalty.factor: column j pays
+ *                mu_k p_j |x_j|; one vector shared by all right-hand sides, on the A that is bound -- no rescaled
+ *                second copy) and the panel tuning key "penalty" (bpgl_panel_get_tuning
+ *                only).  Opt-in: with it off every kernel that existed is unchanged, bit for bit, and a vector
+ *                of ones gives the same bits as off.  bpgl_panel_scratch_bytes grows by the factors' piece, laid
+ *                out after everything that existed (8 n + 256 bytes). */
 int bpgl_version(void);
 
 /*
@@ -564,6 +570,36 @@ int bpgl_panel_intercept(bpgl_panel* ctx, double* out);
  * Legal any time after bpgl_panel_bind (BPGL_E_STATE before it; BPGL_E_ARG on a null context).
  */
 int bpgl_panel_set_positive(bpgl_panel* ctx, int on);
+/*
+ * Penalty factors (since ABI 309): with `pen` non-NULL every right-hand side solves
+ *   min 1/2 || w_k o (A x - b_k) ||^2 + mu_k sum_j p_j |x_j|
+ * (with the row mask, the intercept's profiling and / or x >= 0 when those are installed).  pen: device fp64 [n],
+ * global column order (feature block b holds pen[b w .. (b + 1) w)), one vector for all right-hand sides; it is
+ * copied into the context's scratch and the call returns when the copy is done, so the caller's buffer is free after it.  NULL switches it off.
+ * The factors are used as given: there is no renormalisation to sum p = n (glmnet rescales; multiply by
+ * n / sum p before the call for its convention).  Every entry must be finite and > 0: a validation kernel reads
+ * the vector (one readback: a set-up call) and BPGL_E_ARG is returned, with nothing changed -- the factors
+ * installed before stay in force -- when one is not.  (p_j = 0, an unpenalised column, makes the scaled residual
+ * dual infeasible and needs profiling out as the intercept does; p_j = inf is a column to leave out.)
+ * With tau_j = mu_k p_j and d_j the diag in effect, only the pass-1 shrink and two certificate kernels change:
+ *   prox          x^_j = S(d_j x_j - g_j, tau_j) / d_j (max(0, .) with x >= 0; 0 where 1 / d_j is stored as 0)
+ *   norms         sbx = sum_j p_j |x_j + D'_j|, sx = sum_j p_j |x_j|; the line search rs + mu (sbx - sx) is
+ *                 unchanged and stays the exact line search of the weighted objective along D'
+ *   error record  max_j |g_j - clip(g_j - x_j, -tau_j, tau_j)| (with x >= 0: |x_j - max(0, x_j - g_j - tau_j)|)
+ *   certificate   primal = 1/2 |r|^2 + mu sum_j p_j |x_j|; out[8 k + 4] is max_j |g_j| / p_j (max_j (-g_j)+ / p_j
+ *                 with x >= 0) instead of ||g||_inf; scale = min(1, mu / that), so theta = scale r has
+ *                 |a_j . theta| <= mu p_j; dual and gap keep their formulas
+ *   screen        score_j = scale |g_j| + sqrt(d_j) sqrt(2 max(gap, 0)) (-g_j for |g_j| with x >= 0),
+ *                 keep_j = !(score_j < mu_k p_j)
+ * At x = 0 out[8 k + 4] is max_j |a_j . b| / p_j: above it x = 0 is optimal (mu_max).  Pass 2, the fold, the
+ * line search, the updates, the carried gradient and every other certificate kernel are the unchanged kernels.
+ * A vector of ones computes the bits that NULL computes (mu * 1.0 and 1.0 * |x| are exact).
+ * It invalidates the solver and drops the graphs exactly as bpgl_panel_set_positive does (bpgl_panel_step /
+ * bpgl_panel_gap return BPGL_E_STATE until the next reset); bpgl_panel_bind switches it off.
+ * bpgl_panel_get_tuning("penalty") reports it.  With it off every result is bitwise what ABI 308 computes.
+ * Legal any time after bpgl_panel_bind (BPGL_E_STATE before it; BPGL_E_ARG on a null context).
+ */
+int bpgl_panel_set_penalty(bpgl_panel* ctx, const double* pen);
 /*
  * Warm start (since ABI 306): bpgl_panel_reset at a given iterate.
  * X0: device fp32 [nblock][nrhs][w] (the layout of bpgl_panel_x), 16-byte aligned, caller-owned.

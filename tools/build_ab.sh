@@ -12,9 +12,12 @@ else
   git -C $R archive $REF convex_optimization_amd/csrc include | tar -x -C $SRC
 fi
 mkdir -p $R/build_ab
-# the library's translation units: the Makefile's; a ref from before ABI 308 has no bpgl_panel_pos.hip
+# the library's translation units: the Makefile's; a ref from before ABI 308 has no bpgl_panel_pos.hip, one from
+# before ABI 309 no bpgl_panel_pen.hip / bpgl_panel_penpos.hip
 UNITS="$SRC/convex_optimization_amd/csrc/bpgl.hip $SRC/convex_optimization_amd/csrc/bpgl_panel_abi.hip"
-[ -f $SRC/convex_optimization_amd/csrc/bpgl_panel_pos.hip ] && UNITS="$UNITS $SRC/convex_optimization_amd/csrc/bpgl_panel_pos.hip"
+for u in bpgl_panel_pos bpgl_panel_pen bpgl_panel_penpos; do
+  [ -f $SRC/convex_optimization_amd/csrc/$u.hip ] && UNITS="$UNITS $SRC/convex_optimization_amd/csrc/$u.hip"
+done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared "$@" -I$SRC/include $UNITS \
     -o $R/build_ab/$NAME.so -lrccl
 rm -rf $SRC
