@@ -496,6 +496,116 @@ def penalty_duality_gap(A, b, w, x, mu, p, diag=None, intercept=False, positive=
 
 
 # ---------------------------------------------------------------------------
+# Observation weights: min 1/2 sum_i w_i (a_i . x - b_i)^2 + mu sum_j p_j |x_j| with
+# w_i in [0, 1], with or without the intercept's profiling (then over the weighted mean), the sign constraint and the
+# penalty factors.  The host restatement of bpgl_panel_set_row_weights' solver and certificate; one feature block.
+# ---------------------------------------------------------------------------
+def _row_weights(w, m):
+    w = np.asarray(w, dtype=np.float64).reshape(-1)
+    if w.size != m or not np.all(np.isfinite(w) & (w >= 0.0) & (w <= 1.0)):
+        raise ValueError("row weights: m entries, each finite and in [0, 1]")
+    return w
+
+
+def _wcentre(w, v):
+    """v - (sum w v / sum w) at every row (unweighted); v itself when sum w = 0."""
+    nw = float(w.sum())
+    return v - (float(w @ v) / nw if nw > 0 else 0.0)
+
+
+def weighted_panel_iterate(A, b, w, mu, iters, diag=None, x0=None, intercept=False, positive=False, p=None):
+    """``iters`` updates (one feature block) of the panel's iteration on the weighted problem of one right-hand
+    side, in fp64.  The carried residual is R^ = w o (A x - b) (w o (e - ebar_w) with ``intercept``, ebar_w the
+    weighted mean); G = A^T R^; the prox of ``penalty_panel_iterate`` with ``diag`` (default the FULL column norms,
+    ``centred_diag(A)`` with ``intercept``: d_j >= sum_i w_i a_ij^2 because w <= 1); s = A D and s^ = w o s; the exact
+    line search of the weighted objective along D, gamma = clip(-(R^ . s + mu (sum p |x + D| - sum p |x|)) /
+    (s . s^ - c sum s^), 0, 1) with c = sum s^ / sum w under ``intercept`` and 0 otherwise (gamma = 0 when the
+    curvature is <= 0); x += gamma D and R^ += gamma (s^ - c w).  ``w``: (m,), every entry finite and in [0, 1]
+    (ValueError otherwise).  ``p`` None: all ones.  With ``positive`` ``x0`` is projected to max(x0, 0).  Returns
+    dict(x, r[, intercept]) with r = R^ and intercept = -sum w (A x - b) / sum w."""
+    A = np.asarray(A, dtype=np.float64)
+    m, n = A.shape
+    b = np.asarray(b, dtype=np.float64).reshape(-1)
+    w = _row_weights(w, m)
+    nw = float(w.sum())
+    mu = float(mu)
+    pw = np.ones(n) if p is None else _penalty(p, n)
+    if diag is None:
+        dg = centred_diag(A) if intercept else np.square(A).sum(axis=0)
+    else:
+        dg = np.asarray(diag, dtype=np.float64).reshape(-1)
+    with np.errstate(divide="ignore"):
+        rec = np.where(dg > 0, 1.0 / np.where(dg > 0, dg, 1.0), 0.0)
+    x = np.zeros(n) if x0 is None else np.array(x0, dtype=np.float64).reshape(-1)
+    if positive:
+        x = np.maximum(x, 0.0)
+    e = A @ x - b
+    R = w * (_wcentre(w, e) if intercept else e)
+    for _ in range(int(iters)):
+        g = A.T @ R
+        rx = dg * x - g
+        Bx = rec * (np.sign(rx) * np.maximum(np.abs(rx) - mu * pw, 0))
+        if positive:
+            Bx = np.maximum(Bx, 0.0)
+        D = Bx - x
+        s = A @ D
+        sh = w * s
+        sm = float(sh.sum())
+        c = (sm / nw if nw > 0 else 0.0) if intercept else 0.0
+        l1d = np.where(x * Bx > 0, np.sign(x) * D, np.abs(Bx) - np.abs(x))   # as in penalty_panel_iterate
+        r1 = R @ s + mu * float(pw @ l1d)
+        r2 = s @ sh - c * sm
+        gamma = 0.0 if r2 <= 0 else float(np.clip(-r1 / r2, 0, 1))
+        x = x + gamma * D
+        R = R + gamma * (sh - c * w)
+    out = dict(x=x, r=R)
+    if intercept:
+        e = A @ x - b
+        out["intercept"] = -(float(w @ e) / nw) if nw > 0 else 0.0
+    return out
+
+
+def weighted_duality_gap(A, b, w, x, mu, diag=None, intercept=False, positive=False, p=None, hold=None):
+    """The certificate of the weighted problem at x (x >= 0 with ``positive``): e = A x - b (minus its weighted mean
+    with ``intercept``), r = w o e, g = A^T r; primal = 1/2 sum w e^2 + mu sum p_j |x_j|, and with gnorm_inf =
+    max_j |g_j| / p_j (max_j (-g_j)+ / p_j with ``positive``) and scale = min(1, mu / gnorm_inf) (1 when that is 0),
+    dual = -1/2 scale^2 sum w e^2 - scale sum w e b, gap = primal - dual.  The dual point is theta_i = scale
+    sqrt(w_i) e_i of the problem on (diag(sqrt w) A, sqrt(w) o b); it is never formed.  The gap-safe score is
+    scale |g_j| + sqrt(d_j) sqrt(2 max(gap, 0)) (-g_j with ``positive``), keep_j = not (score_j < mu p_j), with ``diag``
+    (default the FULL column norms, ``centred_diag(A)`` with ``intercept``, safe because w <= 1).  holdout_sse =
+    sum_i h_i (a_i . x + intercept - b_i)^2 with ``hold`` = h >= 0 (default 1 where w = 0, else 0); intercept =
+    -sum w (A x - b) / sum w with ``intercept``, else 0."""
+    A = np.asarray(A, dtype=np.float64)
+    m, n = A.shape
+    b = np.asarray(b, dtype=np.float64).reshape(-1)
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    w = _row_weights(w, m)
+    nw = float(w.sum())
+    mu = float(mu)
+    pw = np.ones(n) if p is None else _penalty(p, n)
+    h = (w == 0.0).astype(np.float64) if hold is None else np.asarray(hold, dtype=np.float64).reshape(-1)
+    e = A @ x - b
+    c = (float(w @ e) / nw if nw > 0 else 0.0) if intercept else 0.0
+    ec = e - c
+    r = w * ec
+    g = A.T @ r
+    wee = float(r @ ec)
+    primal = 0.5 * wee + mu * float(pw @ np.abs(x))
+    ga = np.where(g > 0, 0.0, -g) if positive else np.abs(g)
+    gn = float(np.max(ga / pw))       # NaN propagates
+    scale = min(1.0, mu / gn) if gn > 0.0 else 1.0
+    dual = -0.5 * scale * scale * wee - scale * float(r @ b)
+    gap = primal - dual
+    if diag is None:
+        dg = centred_diag(A) if intercept else np.square(A).sum(axis=0)
+    else:
+        dg = np.asarray(diag, dtype=np.float64).reshape(-1)
+    score = scale * (-g if positive else np.abs(g)) + np.sqrt(dg) * np.sqrt(2.0 * np.maximum(gap, 0.0))
+    return dict(primal=primal, dual=dual, gap=gap, scale=scale, gnorm_inf=gn, holdout_sse=float(h @ (ec * ec)),
+                intercept=-c if (intercept and nw > 0) else 0.0, score=score, keep=~(score < mu * pw), g=g, r=r)
+
+
+# ---------------------------------------------------------------------------
 # Compaction of a screened panel (DESIGN.md section 12).
 # ---------------------------------------------------------------------------
 def compaction_columns(keep_union, q):

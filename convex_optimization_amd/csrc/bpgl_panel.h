@@ -115,6 +115,9 @@ struct PanelParams {
     double* lss;        // [m / kLspRows][k]  line-search partials: sum s (beside lsp's r.s, s.s)
     double* cshift;     // [k]  c = sum s / n_w of the last line search, published beside gamma
     const double* nw;   // [k]  rows in each RHS's objective (0 for an all-zero mask column)
+    // observation weights (bpgl_panel_set_row_weights): only the weighted (WT) kernel variants read
+    // them; nw is then sum_i w_i
+    const double* Wt;   // [k][m] w in [0, 1]: the row's weight in that RHS's objective; null without weights
 };
 
 // a thread's 4 consecutive rows of a masked RHS: the slab sums of held-out rows become 0 by select
@@ -129,6 +132,35 @@ __device__ __forceinline__ void panel_mask4(unsigned wv, double (&s)[4]) {
 __device__ __forceinline__ void panel_centre4(unsigned wv, double c, double (&s)[4]) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) s[q] = ((wv >> (8 * q)) & 0xffu) ? s[q] - c : 0.0;
+}
+
+// observation weights (the WT variants): a thread's 4 consecutive rows' weights of one RHS, two
+// 16-byte loads
+__device__ __forceinline__ void panel_ld_weight4(const double* wp, double (&w)[4]) {
+    const double2 w01 = *reinterpret_cast<const double2*>(wp);
+    const double2 w23 = *reinterpret_cast<const double2*>(wp + 2);
+    w[0] = w01.x; w[1] = w01.y; w[2] = w23.x; w[3] = w23.y;
+}
+// the weighted line-search partials of those rows, and the fold: rs = sum R^ s with the UNWEIGHTED s (R^ = w o (A x - b)
+// carries the one factor w the numerator takes), then s becomes s^ = w o s and ss = sum s s^ -- not s^ . s^ and not
+// R^ . s^, which would square w.  With w in {0, 1} both are the sums panel_mask4 + panel_ls_partial4 form (R^ is 0 where
+// w is), term for term in the same order.
+__device__ __forceinline__ void panel_ls_weight4(const double (&r)[4], const double (&w)[4], double (&s)[4], double& rs,
+                                                 double& ss) {
+    rs = 0.0, ss = 0.0;
+    rs = fma(r[0], s[0], rs); rs = fma(r[1], s[1], rs);
+    rs = fma(r[2], s[2], rs); rs = fma(r[3], s[3], rs);
+    const double u[4] = {s[0], s[1], s[2], s[3]};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) s[q] = w[q] * u[q];
+    ss = fma(u[0], s[0], ss); ss = fma(u[1], s[1], ss);
+    ss = fma(u[2], s[2], ss); ss = fma(u[3], s[3], ss);
+}
+// intercept with weights: the same rows of s^ as the centred step s^ - c w (c = sum s^ / sum w), which is what the R
+// update and the carried operand take; one fma per row in both update kernels, so they agree bitwise (w = 1: s - c)
+__device__ __forceinline__ void panel_centre_weight4(const double (&w)[4], double c, double (&s)[4]) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) s[q] = fma(-c, w[q], s[q]);
 }
 
 constexpr int kLspRows = 1024;    // rows per line-search partial
@@ -1117,9 +1149,12 @@ __device__ __forceinline__ void panel_publish_sums(const PanelParams& p, int rhs
 // the line-search partials, so the update kernels see the masked S and need no mask of their own.
 // IC (with MK, mode 1): the intercept's third partial, sum s of the masked S per group, and the line search
 // that uses it (panel_step_rhs<true, true>); S is stored masked but uncentred (k_panel_update1<true> centres).
-template <bool MK, bool IC = false>
+// WT (mode 1 only, instead of MK; the variants of bpgl_panel_wt.hip): the weighted fold -- the partials of
+// panel_ls_weight4, and s^ = w o s is what is stored, summed (IC) and handed to the update kernels.
+template <bool MK, bool IC = false, bool WT = false>
 __global__ __launch_bounds__(kThreads) void k_panel_reduce(PanelParams p, double* __restrict__ Sout, int mode) {
-    static_assert(!IC || MK, "the intercept runs on the masked fold");
+    static_assert(!IC || MK || WT, "the intercept runs on the masked or the weighted fold");
+    static_assert(!(MK && WT), "a mask and weights are alternatives");
     const int rhs = blockIdx.x % p.k;
     const int grp = blockIdx.x / p.k;
     const long long i = (long long)grp * kLspRows + 4 * threadIdx.x;
@@ -1134,15 +1169,23 @@ __global__ __launch_bounds__(kThreads) void k_panel_reduce(PanelParams p, double
         const double2 r23 = *reinterpret_cast<const double2*>(rp + 2);
         unsigned wv = 0;
         if constexpr (MK) wv = *reinterpret_cast<const unsigned*>(p.W + (long long)rhs * p.m + i);
+        double wq[4] = {0.0, 0.0, 0.0, 0.0};
+        if constexpr (WT) panel_ld_weight4(p.Wt + (long long)rhs * p.m + i, wq);
         const double4 t = panel_slab_sum4(p.Sslab + (long long)rhs * p.m + i, (long long)p.k * p.m, p.kchunks);
         double s[4] = {t.x, t.y, t.z, t.w};
         if constexpr (MK) panel_mask4(wv, s);
         const long long e = (long long)rhs * p.m + i;
+        if constexpr (WT) {
+            const double r[4] = {r01.x, r01.y, r23.x, r23.y};
+            panel_ls_weight4(r, wq, s, rs, ss);   // s is s^ from here on
+        }
         put(Sout, e, make_double2(s[0], s[1]));
         put(Sout, e + 2, make_double2(s[2], s[3]));
+        if constexpr (!WT) {
         if (mode) {
             const double r[4] = {r01.x, r01.y, r23.x, r23.y};
             panel_ls_partial4(r, s, rs, ss);
+        }
         }
         if constexpr (IC) panel_sum_waves(s, panel_sum_rows<1>()[0]);   // whole waves are in or out: m % 256 == 0
     } else if constexpr (IC) {
@@ -1370,8 +1413,11 @@ __global__ __launch_bounds__(kThreads) void k_panel_update(PanelParams p, int cf
 // A thread owns 4 consecutive residual rows.  Also bumps t.
 // IC (the intercept): the stored S is the masked one; the rows' mask word and the line search's c make
 // it P_w s (panel_centre4) before the same update.
-template <bool IC = false>
+// WT (with IC; without the intercept the weighted solver runs k_panel_update1<false> on the stored s^): the stored S is
+// s^ = w o s, centred as s^ - c w (panel_centre_weight4) from the rows' weights.
+template <bool IC = false, bool WT = false>
 __global__ __launch_bounds__(kThreads) void k_panel_update1(PanelParams p, int cflag) {
+    static_assert(!WT || IC, "only the intercept's update reads the weights");
     const long long nr = (long long)p.k * p.m;
     const unsigned ur = (unsigned)(nr / 4), m4 = (unsigned)(p.m / 4);
     for (unsigned v = blockIdx.x * kThreads + threadIdx.x; v < ur; v += gridDim.x * kThreads) {
@@ -1385,7 +1431,11 @@ __global__ __launch_bounds__(kThreads) void k_panel_update1(PanelParams p, int c
         const double2 s23 = *reinterpret_cast<const double2*>(p.S + e + 2);
         const double r[4] = {r01.x, r01.y, r23.x, r23.y};
         double s[4] = {s01.x, s01.y, s23.x, s23.y};
-        if constexpr (IC) panel_centre4(*reinterpret_cast<const unsigned*>(p.W + e), p.cshift[rhs], s);
+        if constexpr (WT) {
+            double wq[4];
+            panel_ld_weight4(p.Wt + e, wq);
+            panel_centre_weight4(wq, p.cshift[rhs], s);
+        } else if constexpr (IC) panel_centre4(*reinterpret_cast<const unsigned*>(p.W + e), p.cshift[rhs], s);
         panel_r_update4(p, cflag, e, re, g, r, s, panel_carry_e(p, cflag, e));
     }
     if (blockIdx.x == 0 && threadIdx.x < 64) panel_bump_t<false>(p, true);
@@ -1411,10 +1461,14 @@ __global__ __launch_bounds__(kThreads) void k_panel_update1(PanelParams p, int c
 // IC (with MK; the intercept): k_panel_reduce<true, true>'s third partial per group; the RHS's last block
 // publishes c beside gamma before `ready`, the waiting blocks read it where they read gamma, and every block
 // turns its masked S into P_w s (panel_centre4, from the mask words it kept) before the update.
+// WT (instead of MK; the variants of bpgl_panel_wt.hip): k_panel_reduce<false, IC, true>'s weighted fold and partials
+// (panel_ls_weight4), the weights loaded with R; with IC every block loads its rows' weights again after the wait (they
+// are not kept in registers across it: 8 VGPRs per group) and centres s^ as s^ - c w.  Same grid, waits and failure path.
 constexpr unsigned kPanelPolls = 1u << 20;
-template <int U, bool MK = false, bool IC = false>
+template <int U, bool MK = false, bool IC = false, bool WT = false>
 __global__ __launch_bounds__(kThreads) void k_panel_reduce_upd(PanelParams p, int cflag, int G) {
-    static_assert(!IC || MK, "the intercept runs on the masked fold");
+    static_assert(!IC || MK || WT, "the intercept runs on the masked or the weighted fold");
+    static_assert(!(MK && WT), "a mask and weights are alternatives");
     const int rhs = blockIdx.x % p.k;
     const int g = blockIdx.x / p.k;
     double na = 0.0, nb = 0.0, ne = 0.0;
@@ -1423,6 +1477,7 @@ __global__ __launch_bounds__(kThreads) void k_panel_reduce_upd(PanelParams p, in
     double s[U][4], r[U][4];
     float4 ev[U];
     unsigned wk[U];   // (IC) the groups' mask words, kept for the centring
+    double wrs[U], wss[U];   // (WT) the groups' weighted partials, formed where the weights are at hand
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const long long e = (long long)rhs * p.m + (long long)(g * U + u) * kLspRows + 4 * threadIdx.x;
@@ -1432,17 +1487,21 @@ __global__ __launch_bounds__(kThreads) void k_panel_reduce_upd(PanelParams p, in
         ev[u] = panel_carry_e(p, cflag, e);
         unsigned wv = 0;
         if constexpr (MK) wv = *reinterpret_cast<const unsigned*>(p.W + e);
+        double wq[4] = {0.0, 0.0, 0.0, 0.0};
+        if constexpr (WT) panel_ld_weight4(p.Wt + e, wq);
         const double4 t = panel_slab_sum4(p.Sslab + e, cstride, p.kchunks);
         s[u][0] = t.x; s[u][1] = t.y; s[u][2] = t.z; s[u][3] = t.w;
         if constexpr (MK) panel_mask4(wv, s[u]);
         if constexpr (IC) wk[u] = wv;
+        if constexpr (WT) panel_ls_weight4(r[u], wq, s[u], wrs[u], wss[u]);   // s[u] is s^ from here on
     }
     // per-group line-search partials, in k_panel_reduce's order
     __shared__ double sr[U][kWaves], sq[U][kWaves];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         double rs, ss;
-        panel_ls_partial4(r[u], s[u], rs, ss);
+        if constexpr (WT) rs = wrs[u], ss = wss[u];
+        else panel_ls_partial4(r[u], s[u], rs, ss);
         panel_ls_waves(rs, ss, sr[u], sq[u]);
     }
     if constexpr (IC) {
@@ -1492,7 +1551,11 @@ __global__ __launch_bounds__(kThreads) void k_panel_reduce_upd(PanelParams p, in
     for (int u = 0; u < U; ++u) {
         const long long e = (long long)rhs * p.m + (long long)(g * U + u) * kLspRows + 4 * threadIdx.x;
         const long long re = (long long)rhs * p.ldr + (e - (long long)rhs * p.m);
-        if constexpr (IC) panel_centre4(wk[u], csh, s[u]);
+        if constexpr (WT && IC) {
+            double wq[4];
+            panel_ld_weight4(p.Wt + e, wq);
+            panel_centre_weight4(wq, csh, s[u]);
+        } else if constexpr (IC) panel_centre4(wk[u], csh, s[u]);
         panel_r_update4(p, cflag, e, re, gm, r[u], s[u], ev[u]);
     }
     // every RHS's err_rhs is published (sc1): end the iteration

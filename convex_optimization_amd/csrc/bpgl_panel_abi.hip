@@ -16,6 +16,7 @@
 #include "bpgl_panel_gap.h"
 #include "bpgl_panel_pos.h"
 #include "bpgl_panel_pen.h"
+#include "bpgl_panel_wt.h"
 
 using namespace bpgl;
 using namespace bpgl_host;
@@ -28,7 +29,7 @@ constexpr int kPanelKinds = 5;   // pass1, pass2, reduce, step, update
 // byte offsets of the scratch regions (panel_layout), in the order they are laid out
 struct PanelLayout {
     int64_t st, Rh, Rl, Dh, Dl, X, Ax, B, R, diag, rec, Sslab, S, norms, lsp, mu, gamma, err_rhs, cnt, ready, lsdone, Gc,
-        Sh, Ec, At, A1t, gpart, gparts, gcounts, gres, W, Bh, ghold, lss, cshift, nw, bmean, gipart, gicp, pen, total;
+        Sh, Ec, At, A1t, gpart, gparts, gcounts, gres, W, Bh, ghold, lss, cshift, nw, bmean, gipart, gicp, pen, Wt, Hd, gE, total;
 };
 
 struct bpgl_panel {
@@ -61,6 +62,8 @@ struct bpgl_panel {
     bool icpt = false;            // bpgl_panel_set_intercept: the intercept (IC) kernel variants run (always with `masked`)
     bool positive = false;        // bpgl_panel_set_positive: x >= 0 (the POS pass-1 variants, the one-sided certificate)
     bool penalty = false;         // bpgl_panel_set_penalty: per-column l1 weights (the PF pass-1 variants, the weighted certificate)
+    bool weighted = false;        // bpgl_panel_set_row_weights: observation weights (the WT fold variants; never with `user_mask`,
+                                  // and `masked` is then false: the weights stand where the mask would)
     bool icpt_valid = false;      // a bpgl_panel_gap has run since the last reset: icpt_host is its beta0
     std::vector<double> icpt_host;
     char* scratch = nullptr;      // the caller's scratch and its layout (bpgl_panel_bind)
@@ -95,14 +98,16 @@ int pgap_prod(bpgl_panel* c, const PanelGapArgs& a, dim3 grid) {
     hipLaunchKernelGGL(prod, grid, blk, 0, c->stream, a);
     LAUNCH_CHECK("k_pgap_prod");
     const dim3 fgrid((unsigned)cdiv((int64_t)c->k * (PROD == 1 ? c->m : c->n), kThreads));
-    if (PROD == 1 && c->icpt) hipLaunchKernelGGL((k_pgap_fold<1, true, true>), fgrid, blk, 0, c->stream, a);
+    if (PROD == 1 && c->weighted) hipLaunchKernelGGL(bpgl_wt::gap_fold(c->icpt), fgrid, blk, 0, c->stream, a);
+    else if (PROD == 1 && c->icpt) hipLaunchKernelGGL((k_pgap_fold<1, true, true>), fgrid, blk, 0, c->stream, a);
     else if (PROD == 1 && c->masked) hipLaunchKernelGGL((k_pgap_fold<1, true>), fgrid, blk, 0, c->stream, a);
     else hipLaunchKernelGGL((k_pgap_fold<PROD, false>), fgrid, blk, 0, c->stream, a);
     LAUNCH_CHECK("k_pgap_fold");
     if (PROD == 1 && c->icpt) {   // the fold left the uncentred e: its in-row mean per RHS, then P_w e and the held-out squares
         hipLaunchKernelGGL(k_pgap_icpt_mean, dim3((unsigned)c->k), blk, 0, c->stream, a, (long long)(c->m / kThreads));
         LAUNCH_CHECK("k_pgap_icpt_mean");
-        hipLaunchKernelGGL(k_pgap_centre, fgrid, blk, 0, c->stream, a);
+        if (c->weighted) hipLaunchKernelGGL(bpgl_wt::gap_centre(), fgrid, blk, 0, c->stream, a);
+        else hipLaunchKernelGGL(k_pgap_centre, fgrid, blk, 0, c->stream, a);
         LAUNCH_CHECK("k_pgap_centre");
     }
     return 0;
@@ -166,6 +171,11 @@ PanelLayout panel_layout(const bpgl_panel* c) {
     // the penalty factors (bpgl_panel_set_penalty): p [n] fp64 and, behind them, the validation kernel's flag.
     // After everything else once more.
     L.pen = k.take(8 * c->n + 256);
+    // the observation weights (bpgl_panel_set_row_weights): w and the scoring weights h [k][m] fp64, the validation
+    // kernel's flag behind them, and the certificate's unweighted e.  After everything else once more.
+    L.Wt = k.take(8 * km);
+    L.Hd = k.take(8 * km + 256);
+    L.gE = k.take(8 * km);
     L.total = k.off;
     return L;
 }
@@ -232,7 +242,8 @@ bool panel_fused_geo(const bpgl_panel* c, int* G, int* U) {
 // the k_panel_reduce_upd variant of a geometry: what panel_fuse_check asks the occupancy of is what
 // panel_reduce_upd launches
 using PanelFusedFn = void (*)(PanelParams, int, int);
-PanelFusedFn panel_fused_fn(int U, bool masked, bool icpt) {
+PanelFusedFn panel_fused_fn(int U, bool masked, bool icpt, bool weighted) {
+    if (weighted) return bpgl_wt::fused(U, icpt);   // the WT variants, from their own code object
     return dispatch<1, 2, 4>(U, [&](auto u) -> PanelFusedFn {
         if (icpt) return &k_panel_reduce_upd<decltype(u)::value, true, true>;
         return masked ? &k_panel_reduce_upd<decltype(u)::value, true> : &k_panel_reduce_upd<decltype(u)::value, false>;
@@ -241,21 +252,21 @@ PanelFusedFn panel_fused_fn(int U, bool masked, bool icpt) {
 int panel_reduce_upd(bpgl_panel* c, int cflag) {
     int G = 0, U = 0;
     (void)panel_fused_geo(c, &G, &U);
-    hipLaunchKernelGGL(panel_fused_fn(U, c->masked, c->icpt), dim3((unsigned)(c->k * G)), dim3(kThreads), 0, c->stream, c->p,
+    hipLaunchKernelGGL(panel_fused_fn(U, c->masked, c->icpt, c->weighted), dim3((unsigned)(c->k * G)), dim3(kThreads), 0, c->stream, c->p,
                        cflag, G);
     LAUNCH_CHECK("k_panel_reduce_upd");
     return 0;
 }
 // the fused reduce + update needs its k x G blocks resident together: on the CUs the stream may use
 // (a CU-masked stream from bpgl_stream_create gets fewer), else the two-kernel form runs.  The
-// occupancy is that of the variant that will run (masked or not, with the intercept or not), so
-// bpgl_panel_set_row_mask and bpgl_panel_set_intercept repeat it.
+// occupancy is that of the variant that will run (masked, weighted or neither, with the intercept or not), so
+// bpgl_panel_set_row_mask, bpgl_panel_set_row_weights and bpgl_panel_set_intercept repeat it.
 void panel_fuse_check(bpgl_panel* c) {
     int G = 0, U = 0, nb = 0;
     c->fuse_ok = 0;
     c->fuse_cus = 0;
     if (!panel_fused_geo(c, &G, &U)) return;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)panel_fused_fn(U, c->masked, c->icpt), kThreads, 0) !=
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)panel_fused_fn(U, c->masked, c->icpt, c->weighted), kThreads, 0) !=
         hipSuccess) {
         (void)hipGetLastError();   // the query's own error only
         return;
@@ -266,7 +277,8 @@ void panel_fuse_check(bpgl_panel* c) {
 // mode 0 (bpgl_panel_mm) is always the unmasked fold
 int panel_reduce(bpgl_panel* c, double* out, int mode) {
     const dim3 grid((unsigned)(c->k * cdiv(c->m, kLspRows)));
-    if (mode && c->icpt) hipLaunchKernelGGL((k_panel_reduce<true, true>), grid, dim3(kThreads), 0, c->stream, c->p, out, mode);
+    if (mode && c->weighted) hipLaunchKernelGGL(bpgl_wt::reduce(c->icpt), grid, dim3(kThreads), 0, c->stream, c->p, out, mode);
+    else if (mode && c->icpt) hipLaunchKernelGGL((k_panel_reduce<true, true>), grid, dim3(kThreads), 0, c->stream, c->p, out, mode);
     else if (mode && c->masked) hipLaunchKernelGGL(k_panel_reduce<true>, grid, dim3(kThreads), 0, c->stream, c->p, out, mode);
     else hipLaunchKernelGGL(k_panel_reduce<false>, grid, dim3(kThreads), 0, c->stream, c->p, out, mode);
     LAUNCH_CHECK("k_panel_reduce");
@@ -292,7 +304,8 @@ int panel_iteration(bpgl_panel* c, int64_t it, bool exact = false, bool split_r 
     return c->tm.timed(4, it, [&] {
         if (c->nblock == 1 && c->defer_x) {   // R only; x += gamma D' rides on the next pass-1 epilogue (or the flush)
             const dim3 ug((unsigned)std::min<int64_t>(cdiv((int64_t)c->k * c->m / 4, kThreads), 8192));
-            if (c->icpt) hipLaunchKernelGGL(k_panel_update1<true>, ug, dim3(kThreads), 0, c->stream, c->p, cflag);
+            if (c->icpt && c->weighted) hipLaunchKernelGGL(bpgl_wt::update1_icpt(), ug, dim3(kThreads), 0, c->stream, c->p, cflag);
+            else if (c->icpt) hipLaunchKernelGGL(k_panel_update1<true>, ug, dim3(kThreads), 0, c->stream, c->p, cflag);
             else hipLaunchKernelGGL(k_panel_update1<false>, ug, dim3(kThreads), 0, c->stream, c->p, cflag);
         } else {
             const int64_t n = (int64_t)c->k * c->w / 8 + (int64_t)c->k * c->m / 4;   // work units
@@ -344,6 +357,9 @@ PanelGapArgs pgap_args(const bpgl_panel* c) {
     a.icp = c->at<double>(c->L.gicp);
     a.nw = c->p.nw;
     a.bmean = c->at<double>(c->L.bmean);
+    a.Wt = c->weighted ? c->p.Wt : nullptr;
+    a.Hd = c->at<double>(c->L.Hd);
+    a.E = c->at<double>(c->L.gE);
     return a;
 }
 // bpgl_panel_reset_x0: R = A X - B (w o (A X - B) with a row mask, P_w(A X - B) with the intercept) from the
@@ -373,8 +389,24 @@ int panel_warm_residual(bpgl_panel* c) {
 
 // the mask in effect: the caller's, else (the intercept on) all ones, else none; with the intercept the
 // in-row counts too.  Then the fused form's occupancy check for the variant that will run.
+// With observation weights (never with a caller's mask) no byte mask is in effect: the WT variants read p.Wt, and the
+// intercept's n_w is their sum.
 int panel_install_mask(bpgl_panel* c) {
     unsigned char* W = c->at<unsigned char>(c->L.W);
+    c->p.Wt = c->weighted ? c->at<double>(c->L.Wt) : nullptr;
+    if (c->weighted) {
+        c->masked = false;
+        c->p.W = nullptr;
+        if (c->icpt) {
+            hipLaunchKernelGGL(bpgl_wt::sum_weights(), dim3((unsigned)c->k), dim3(kThreads), 0, c->stream, c->p.Wt,
+                               (long long)c->m, c->at<double>(c->L.nw));
+            LAUNCH_CHECK("k_panel_sum_weights");
+        }
+        c->solver = false;
+        drop_graphs(c);
+        panel_fuse_check(c);
+        return 0;
+    }
     if (c->icpt && !c->user_mask) HIP_TRY(hipMemsetAsync(W, 1, (int64_t)c->k * c->m, c->stream));
     c->masked = c->user_mask || c->icpt;
     c->p.W = c->masked ? W : nullptr;
@@ -529,7 +561,7 @@ int bpgl_panel_bind(bpgl_panel* c, const void* A, int64_t lda, void* scratch, in
     hipLaunchKernelGGL((k_panel_tile<64, 256, false>), dim3((unsigned)((c->m / 64) * (c->n / 256))), dim3(256), 0,
                        c->stream, p.A, p.lda, c->n, c->at<__bf16>(L.A1t));
     LAUNCH_CHECK("k_panel_tile");
-    c->masked = c->user_mask = c->icpt = c->icpt_valid = c->positive = c->penalty = false;   // p.W is null again
+    c->masked = c->user_mask = c->icpt = c->icpt_valid = c->positive = c->penalty = c->weighted = false;   // p.W, p.Wt are null again
     panel_fuse_check(c);
     c->bound = true;
     c->have_diag = false;
@@ -586,11 +618,23 @@ int bpgl_panel_reset_x0(bpgl_panel* c, const double* B, const double* mu, const 
         return fail(BPGL_E_STATE, "the intercept needs one feature block (nblock is %d)", c->nblock);
     if (c->icpt && !c->defer_x)
         return fail(BPGL_E_STATE, "the intercept needs the deferred x update (the tuning key defer_x is 0)");
+    if (c->weighted && c->nblock > 1)
+        return fail(BPGL_E_STATE, "row weights need one feature block (nblock is %d)", c->nblock);
+    if (c->weighted && !c->defer_x)
+        return fail(BPGL_E_STATE, "row weights need the deferred x update (the tuning key defer_x is 0)");
     HIP_TRY(hipSetDevice(c->device));
     PanelParams& p = c->p;
     const int64_t km = (int64_t)c->k * c->m;
     c->icpt_valid = false;
-    if (c->icpt) {   // the stored B is P_w B (so R0 = -P_w B), its in-row mean kept for the certificate; (1 - w) o B as below
+    if (c->weighted && c->icpt) {   // the stored B is w o (b - bmean), bmean the weighted mean; the full B for the certificate
+        hipLaunchKernelGGL(bpgl_wt::centre_b(), dim3((unsigned)c->k), dim3(kThreads), 0, c->stream, B, p.Wt, (long long)c->m,
+                           p.nw, const_cast<double*>(p.B), c->at<double>(c->L.Bh), c->at<double>(c->L.bmean));
+        LAUNCH_CHECK("k_panel_centre_b_wt");
+    } else if (c->weighted) {       // the stored B is w o B (so R0 = -w o B); the full B for the certificate
+        hipLaunchKernelGGL(bpgl_wt::weight_b(), dim3((unsigned)std::min<int64_t>(cdiv(km, kThreads), 2048)), dim3(kThreads),
+                           0, c->stream, B, p.Wt, (long long)km, const_cast<double*>(p.B), c->at<double>(c->L.Bh));
+        LAUNCH_CHECK("k_panel_weight_b");
+    } else if (c->icpt) {   // the stored B is P_w B (so R0 = -P_w B), its in-row mean kept for the certificate; (1 - w) o B as below
         hipLaunchKernelGGL(k_panel_centre_b, dim3((unsigned)c->k), dim3(kThreads), 0, c->stream, B, p.W, (long long)c->m,
                            p.nw, const_cast<double*>(p.B), c->at<double>(c->L.Bh), c->at<double>(c->L.bmean));
         LAUNCH_CHECK("k_panel_centre_b");
@@ -773,6 +817,7 @@ int bpgl_panel_get_tuning(const bpgl_panel* c, const char* key, int64_t* value) 
     else if (!strcmp(key, "g_refresh")) *value = c->g_period;
     else if (!strcmp(key, "positive")) *value = c->positive ? 1 : 0;   // bpgl_panel_set_positive
     else if (!strcmp(key, "penalty")) *value = c->penalty ? 1 : 0;     // bpgl_panel_set_penalty
+    else if (!strcmp(key, "row_weights")) *value = c->weighted ? 1 : 0;   // bpgl_panel_set_row_weights
     else return fail(BPGL_E_ARG, "unknown panel tuning key '%s'", key);
     return 0;
 }
@@ -797,7 +842,40 @@ int bpgl_panel_set_row_mask(bpgl_panel* c, const uint8_t* mask) {
     unsigned char* W = c->at<unsigned char>(c->L.W);
     if (mask) HIP_TRY(hipMemcpyAsync(W, mask, (int64_t)c->k * c->m, hipMemcpyDeviceToDevice, c->stream));
     c->user_mask = mask != nullptr;
+    c->weighted = false;            // a mask and weights are alternatives: the last call wins
     return panel_install_mask(c);   // with the intercept on: all ones when cleared, and the in-row counts again
+}
+
+int bpgl_panel_set_row_weights(bpgl_panel* c, const double* wt, const double* hold) {
+    int rc;
+    if ((rc = panel_ready(c))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const int64_t km = (int64_t)c->k * c->m;
+    if (wt) {
+        // validated where the caller has them, so that refused weights leave what was installed in force
+        double* dw = c->at<double>(c->L.Wt);
+        double* dh = c->at<double>(c->L.Hd);
+        int* flag = reinterpret_cast<int*>(dh + km);
+        int bad = 0;
+        const dim3 grid((unsigned)std::min<int64_t>(cdiv(km, kThreads), 2048));
+        HIP_TRY(hipMemsetAsync(flag, 0, sizeof(int), c->stream));
+        hipLaunchKernelGGL(bpgl_wt::check(), grid, dim3(kThreads), 0, c->stream, wt, hold, (long long)km, flag);
+        LAUNCH_CHECK("k_panel_check_weights");
+        HIP_TRY(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (bad) return fail(BPGL_E_ARG, "every row weight must be finite and in [0, 1], every scoring weight finite and >= 0");
+        if (wt != dw) HIP_TRY(hipMemcpyAsync(dw, wt, 8 * km, hipMemcpyDeviceToDevice, c->stream));
+        if (hold) {
+            if (hold != dh) HIP_TRY(hipMemcpyAsync(dh, hold, 8 * km, hipMemcpyDeviceToDevice, c->stream));
+        } else {
+            hipLaunchKernelGGL(bpgl_wt::default_hold(), grid, dim3(kThreads), 0, c->stream, dw, (long long)km, dh);
+            LAUNCH_CHECK("k_panel_default_hold");
+        }
+        HIP_TRY(hipStreamSynchronize(c->stream));   // a set-up call: done when it returns, so the caller's buffers are free
+    }
+    c->weighted = wt != nullptr;
+    c->user_mask = false;           // a mask and weights are alternatives: the last call wins (also when it clears)
+    return panel_install_mask(c);   // the weight sums with the intercept on; the fused form's occupancy check again
 }
 
 int bpgl_panel_set_intercept(bpgl_panel* c, int on) {
@@ -890,7 +968,10 @@ int bpgl_panel_gap(bpgl_panel* c, double* G_all, double* R_fresh, uint8_t* keep,
     }
     const int nparts = pgap_nparts(c);
     const double* pen = c->at<double>(L.pen);
-    if (c->penalty)
+    if (c->weighted)   // sum w e^2 and sum w e b from the fold's e (pen is read with the factors only)
+        hipLaunchKernelGGL(bpgl_wt::gap_partials(c->positive, c->penalty), dim3((unsigned)nparts, (unsigned)c->k),
+                           dim3(kThreads), 0, c->stream, a, parts, pen);
+    else if (c->penalty)
         hipLaunchKernelGGL(c->positive ? bpgl_pen::gap_partials_pos() : bpgl_pen::gap_partials(),
                            dim3((unsigned)nparts, (unsigned)c->k), dim3(kThreads), 0, c->stream, a, parts, pen);
     else
@@ -899,7 +980,7 @@ int bpgl_panel_gap(bpgl_panel* c, double* G_all, double* R_fresh, uint8_t* keep,
     LAUNCH_CHECK("k_pgap_partials");
     hipLaunchKernelGGL(k_pgap_final, dim3((unsigned)c->k), dim3(kThreads), 0, c->stream, parts, nparts, a.mu, res);
     LAUNCH_CHECK("k_pgap_final");
-    if (c->masked) {   // res[k][7], which k_pgap_final left at 0
+    if (c->masked || c->weighted) {   // res[k][7], which k_pgap_final left at 0
         hipLaunchKernelGGL(k_pgap_holdout, dim3((unsigned)c->k), dim3(kThreads), 0, c->stream, a.hpart,
                            (long long)(c->m / kThreads), res);
         LAUNCH_CHECK("k_pgap_holdout");

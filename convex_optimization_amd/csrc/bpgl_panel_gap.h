@@ -45,6 +45,14 @@
 //                           with POS), so scale = min(1, mu / that) gives |a_j . (scale r)| <= mu p_j; k_pgap_final is
 //                           unchanged
 //   k_pgap_screen_pf        keep_j = not (score_j < mu p_j), the score as above
+// With observation weights w in [0, 1] (bpgl_panel_set_row_weights; B is then stored as w o B, the
+// full B in Bh; the kernels of bpgl_panel_wt.hip):
+//   k_pgap_fold_wt          E[k][i] = e = a_i . x_k - b_ki at every row, Rf = w o e, and per block the scoring partial
+//                           sum h e^2 that k_pgap_holdout consumes; with the intercept the uncentred e and per block
+//                           sum w e for k_pgap_icpt_mean (unchanged: n_w is then sum w), and
+//   k_pgap_centre_wt        E = e - ebar_w, Rf = w o E, the scoring partials from a_i . x + beta0 - b_i
+//   k_pgap_partials_wt      sum w e^2 = sum Rf E and sum w e b = sum E B instead of sum r^2 and sum r b (pgap_partials_body's
+//                           WT flag), in the same walk; with POS and / or PF as their variants have it
 // Every reduction walks its dimension in a fixed order (within a chunk: 32-deep stages in index
 // order, 4 at a time through the MFMA; then the chunks; then wave_sum / wave_max, the waves, the
 // blocks in index order).  No floating-point atomics: two calls on the same state return the same
@@ -100,6 +108,10 @@ struct PanelGapArgs {
     double* icp;          // [2][k]           c' = the in-row mean of what the fold left; beta0
     const double* nw;     // [k]              rows in each RHS's objective
     const double* bmean;  // [k]              the in-row mean of b that the stored P_w B had subtracted
+    // observation weights (null / unread without them): the weighted fold of product 1 and the weighted partials
+    const double* Wt;     // [k][m]           w in [0, 1]
+    const double* Hd;     // [k][m]           the scoring weights h >= 0 of res[k][7]
+    double* E;            // [k][m]           e = a_i . x - b_i (centred with the intercept), unweighted
 };
 
 // bf16 e of 8 in a 16-byte piece -> fp64 (exact)
@@ -341,7 +353,11 @@ __global__ __launch_bounds__(kThreads) void k_pgap_holdout(const double* __restr
 
 // grid (nparts, k); parts[k][nparts][kPgPart].  POS: the dual constraint is one-sided, -a_j . theta <= mu, and
 // the fourth partial is max (-g)+ instead of max |g|
-template <bool POS, bool PF>
+// WT (observation weights; the variants of bpgl_panel_wt.hip): Rf is w o e and the stored B is w o b (both centred with
+// the intercept), so r^2 and r b would carry w twice.  The first two partials are sum w e^2 = sum Rf e and
+// sum w e b = sum e B instead, with e read from a.E, where the weighted fold left it -- never Rf / w.  Same walk, same
+// order: with w in {0, 1} they are the sums of the masked certificate term for term.
+template <bool POS, bool PF, bool WT = false>
 __device__ __forceinline__ void pgap_partials_body(const PanelGapArgs& a, double* __restrict__ parts,
                                                    const double* __restrict__ pen) {
     const int k = blockIdx.y;
@@ -353,8 +369,14 @@ __device__ __forceinline__ void pgap_partials_body(const PanelGapArgs& a, double
     const double* __restrict__ rs = a.R + (long long)k * a.m;
     for (long long i = tid; i < a.m; i += stride) {
         const double r = rf[i];
+        if constexpr (WT) {
+            const double ev = a.E[(long long)k * a.m + i];
+            rr = fma(r, ev, rr);
+            rb = fma(ev, b[i], rb);
+        } else {
         rr = fma(r, r, rr);
         rb = fma(r, b[i], rb);
+        }
         dr = nan_max(dr, fabs(rs[i] - r));
     }
     for (long long j = tid; j < a.n; j += stride) {
@@ -398,6 +420,12 @@ template <bool POS>
 __global__ __launch_bounds__(kThreads) void k_pgap_partials_pf(PanelGapArgs a, double* __restrict__ parts,
                                                                const double* __restrict__ pen) {
     pgap_partials_body<POS, true>(a, parts, pen);
+}
+// ... with observation weights (a.E, beside a.Rf and the stored w o b); pen is read with PF only
+template <bool POS, bool PF>
+__global__ __launch_bounds__(kThreads) void k_pgap_partials_wt(PanelGapArgs a, double* __restrict__ parts,
+                                                               const double* __restrict__ pen) {
+    pgap_partials_body<POS, PF, true>(a, parts, pen);
 }
 
 #ifndef BPGL_PANEL_TEMPLATES_ONLY

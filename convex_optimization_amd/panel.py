@@ -44,6 +44,9 @@ right-hand side's own in-rows inside the fold, and ``lasso_path`` / ``lasso_cv``
 ``PanelLasso.set_penalty_factors`` gives column j the l1 weight p_j > 0 (glmnet's ``penalty.factor``, the adaptive
 lasso's weights; used as given, not renormalised), one vector for all right-hand sides on the A that is bound,
 and ``lasso_path`` / ``lasso_cv`` take ``penalty_factors``.
+``PanelLasso.set_row_weights`` gives every right-hand side observation weights w_i in [0, 1] (glmnet's ``weights``,
+scikit-learn's ``sample_weight``) and scoring weights for the held-out score, on the A that is bound -- no row-rescaled
+copy -- and ``lasso_path`` / ``lasso_cv`` take ``sample_weight`` (any scale, used as given).
 
 All compute goes through libbpgl.so (bpgl_panel_* in include/bpgl.h).
 """
@@ -86,6 +89,7 @@ _PANEL_SIGS = {
     "bpgl_panel_intercept": (ctypes.c_int, [_p, ctypes.POINTER(ctypes.c_double)]),
     "bpgl_panel_set_positive": (ctypes.c_int, [_p, ctypes.c_int]),
     "bpgl_panel_set_penalty": (ctypes.c_int, [_p, _p]),
+    "bpgl_panel_set_row_weights": (ctypes.c_int, [_p, _p, _p]),
 }
 N._SIGS.update(_PANEL_SIGS)
 
@@ -304,6 +308,26 @@ class PanelLasso:
             N.check(_lib().bpgl_panel_set_penalty(self._ctx, N.ptr(self._pen)), "bpgl_panel_set_penalty")
         self.stream.synchronize()
 
+    def set_row_weights(self, weights, holdout=None):
+        """Observation weights per right-hand side (bpgl_panel_set_row_weights; one feature block): column k
+        minimises 1/2 sum_i w_ik (a_i . x - b_ik)^2 + mu sum_j p_j |x_j| (with the intercept -- then profiled over the
+        weighted mean --, x >= 0 and the penalty factors when those are on).  ``weights``: an (m, k) or (m,) array or
+        tensor (one vector serves every column), every entry finite and in [0, 1] (ValueError otherwise, before any
+        device work; scale larger weights by their maximum c and pass mu / c), or None to clear them.  ``holdout``:
+        the scoring weights h >= 0 of ``duality_gap()['holdout_sse']`` = sum_i h_ik (a_i . x + beta0 - b_ik)^2, same
+        shapes; None scores the zero-weight rows with weight 1, the row mask's rule.  Weights and a row mask are
+        alternatives: the last call wins.  A ``solver_reset`` (with the full B) must follow.  ``residual_device`` is
+        then w o (A x - b) and ``duality_gap`` certifies the weighted problems with its usual keys.  0/1 weights compute
+        what ``set_row_mask`` computes, and ``set_row_weights(None)`` restores the plain solver bitwise."""
+        wt = _check_row_weights(weights, self.MAT_HEIGHT, self.nrhs, "weights", 1.0)
+        hd = None if wt is None else _check_row_weights(holdout, self.MAT_HEIGHT, self.nrhs, "holdout", np.inf)
+        with self._on_stream():
+            self._wt = None if wt is None else torch.from_numpy(wt).to(self.device)   # [k][m]
+            self._hd = None if hd is None else torch.from_numpy(hd).to(self.device)
+            N.check(_lib().bpgl_panel_set_row_weights(self._ctx, N.ptr(self._wt), N.ptr(self._hd)),
+                    "bpgl_panel_set_row_weights")
+        self.stream.synchronize()
+
     def solver_step(self, n_iter):
         with self._on_stream():
             N.check(_lib().bpgl_panel_step(self._ctx, int(n_iter)), "bpgl_panel_step")
@@ -413,6 +437,8 @@ class PanelLasso:
 
 
 PANEL_NRHS = (16, 32, 64, 128)
+# the certificate's outputs that scale with the objective (``sample_weight``: the library solves the problem / max omega)
+_SCALED_KEYS = ("primal", "dual", "gap", "gnorm_inf")
 # lasso_path's default: the smallest multiple of 64 iterations at which one certificate costs at most
 # 10 % of the iterations between two of them, measured at 8192 x 65536, k = 128
 PATH_CHECK_EVERY = 192
@@ -464,6 +490,36 @@ def _check_penalty(p, n):
     return pen
 
 
+def _check_row_weights(v, m, k, what, upper):
+    """``v``, (m, k) or (m,), as a contiguous fp64 numpy array [k][m], every entry finite and in [0, ``upper``]
+    (ValueError otherwise); None stays None.  Needs no GPU."""
+    if v is None:
+        return None
+    a = np.array(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float64)   # a copy
+    if a.shape == (int(m),):
+        a = np.repeat(a[:, None], int(k), axis=1)
+    if a.shape != (int(m), int(k)):
+        raise ValueError(f"{what} must be (m, k) = ({int(m)}, {int(k)}) or (m,), got {a.shape}")
+    if not np.all(np.isfinite(a) & (a >= 0.0) & (a <= upper)):
+        raise ValueError(f"every entry of {what} must be finite and " + ("in [0, 1]" if upper == 1.0 else ">= 0"))
+    return np.ascontiguousarray(a.T)
+
+
+def _check_sample_weight(sw, m, Block):
+    """``sample_weight`` of the drivers as an fp64 vector (m,): finite, >= 0, not all zero, and Block = 1
+    (ValueError otherwise); None stays None."""
+    if sw is None:
+        return None
+    om = np.array(sw.detach().cpu().numpy() if isinstance(sw, torch.Tensor) else sw, dtype=np.float64).reshape(-1)
+    if om.size != int(m):
+        raise ValueError(f"sample_weight must have m = {int(m)} entries, got {om.size}")
+    if not np.all(np.isfinite(om) & (om >= 0.0)) or not np.any(om > 0.0):
+        raise ValueError("every sample weight must be finite and >= 0, and not all of them zero")
+    if int(Block) != 1:
+        raise ValueError("sample_weight needs Block = 1")
+    return om
+
+
 def _check_shrink(shrink):
     if not 0.0 <= float(shrink) < 1.0:
         raise ValueError("shrink must lie in [0, 1)")
@@ -483,7 +539,7 @@ def _grid_below(mu_max, n_mus, hi, lo, positive):
 
 
 def _screened_loop(pl, B, mu, target, ITER_MAX, check_every, shrink, mask=None, intercept=False, positive=False,
-                   penalty=None):
+                   penalty=None, weights=None):
     """``_check_loop`` on a freshly reset ``pl`` (reset with ``B``, ``mu``; ``mask``: the (m, k) row mask
     installed on it, or None) with gap-safe compaction, ``ClassLassoScreened``'s rule on a panel: after
     a check that did not stop the loop, the union over the panel's columns of the screen's keep goes
@@ -493,7 +549,8 @@ def _screened_loop(pl, B, mu, target, ITER_MAX, check_every, shrink, mask=None, 
     intercept / the sign constraint, which ``pl`` then has on too) installed there, and the solve continues
     from ``solver_reset(B, mu, x0=X[sel])``.  ``pl`` stays alive; an earlier narrow context is dropped.
     ``penalty``: the (n,) penalty factors installed on ``pl`` (or None); a narrower context gets them gathered with
-    the same columns.
+    the same columns.  ``weights``: the (weights, holdout) pair installed on ``pl`` with ``set_row_weights`` (or None;
+    never with ``mask``); a narrower context gets the same pair.
 
     Returns dict(t, cert, first, reached, x (n, k), active, compactions [(t, n_active after)],
     compact_seconds).  ``reached`` is the loop's own verdict.  After a compaction ``cert`` is one
@@ -533,6 +590,8 @@ def _screened_loop(pl, B, mu, target, ITER_MAX, check_every, shrink, mask=None, 
                 nxt.set_penalty_factors(penalty[active[sel]])
             if mask is not None:
                 nxt.set_row_mask(mask)
+            if weights is not None:
+                nxt.set_row_weights(*weights)
             nxt.solver_reset(B, mu, x0=x0)
             nxt.stream.synchronize()
             cur, active = nxt, active[sel]                        # a narrow `cur` is released here
@@ -555,7 +614,7 @@ def _screened_loop(pl, B, mu, target, ITER_MAX, check_every, shrink, mask=None, 
 
 def lasso_path(A, b, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_BOUND=1e-4, ITER_MAX=4096,
                check_every=PATH_CHECK_EVERY, device=None, x0=None, shrink=0.0, fit_intercept=False, positive=False,
-               penalty_factors=None):
+               penalty_factors=None, sample_weight=None):
     """A regularization path as ONE panel: min 1/2 ||A x - b||^2 + mu ||x||_1 for every mu of a grid,
     on the bf16-stored A, every column of the panel holding the same b.
 
@@ -594,8 +653,17 @@ def lasso_path(A, b, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_BOUND=1e-4
     ``penalty_factors``: an (n,) vector p, every entry finite and > 0 (ValueError
     otherwise); every mu solves min 1/2 ||A x - b||^2 + mu sum_j p_j |x_j| (``PanelLasso.set_penalty_factors``,
     on every narrower context of ``shrink`` gathered with its columns).  Used as given, not renormalised.  With
-    ``mus=None`` mu_max is max_j |a_j . b| / p_j."""
+    ``mus=None`` mu_max is max_j |a_j . b| / p_j.
+
+    ``sample_weight`` (``Block`` must be 1): an (m,) vector omega, every entry finite and >= 0
+    and not all zero (ValueError otherwise); every mu solves min 1/2 sum_i omega_i e_i^2 + mu sum_j p_j |x_j| with
+    e_i = a_i . x - b_i (+ beta0 with ``fit_intercept``, then profiled over the weighted mean).  omega is used as
+    given -- no renormalisation to sum omega = m.  Internally c = max omega, w = omega / c and mu / c go to
+    ``PanelLasso.set_row_weights`` (also on every narrower context of ``shrink``); ``mus``, mu_max, primal, dual, gap,
+    gnorm_inf and the bound GAP_BOUND * 1/2 sum omega b^2 (b centred over the weighted mean with ``fit_intercept``)
+    are in the caller's scale."""
     penalty = _check_penalty(penalty_factors, int(A.shape[1]))
+    omega = _check_sample_weight(sample_weight, int(A.shape[0]), Block)
     if int(check_every) <= 0:
         raise ValueError("check_every must be > 0")
     shrink = _check_shrink(shrink)
@@ -624,26 +692,36 @@ def lasso_path(A, b, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_BOUND=1e-4
         pl.set_positive(True)
     if penalty is not None:
         pl.set_penalty_factors(penalty)
+    # sample weights: the library solves the problem divided by c = max omega (w = omega / c in [0, 1], mu / c); `grid`
+    # and every returned scalar stay in the caller's scale
+    cw = 1.0 if omega is None else float(omega.max())
+    weights = None if omega is None else (omega / cw, None)
+    if weights is not None:
+        pl.set_row_weights(*weights)
     B = np.repeat(b[:, None], k, axis=1)
     mu_max = None
     if grid is None:
         pl.solver_reset(B, 1.0)
-        mu_max = float(pl.duality_gap(screen=False)["gnorm_inf"][0])
+        mu_max = cw * float(pl.duality_gap(screen=False)["gnorm_inf"][0])
         grid, _ = pad_mus(_grid_below(mu_max, n_given, hi, lo, positive))
     if x0 is None:
-        pl.solver_reset(B, grid)
+        pl.solver_reset(B, grid / cw)
     else:
         pad = np.repeat(x0[:, [int(np.argmax(grid[:n_given]))]], k - n_given, axis=1)
-        pl.solver_reset(B, grid, x0=np.concatenate([x0, pad], axis=1))
-    bc = b - b.mean() if fit_intercept else b
-    target = float(GAP_BOUND) * 0.5 * float(bc @ bc)
-    run = _screened_loop(pl, B, grid, target, ITER_MAX, check_every, shrink, intercept=bool(fit_intercept),
-                         positive=bool(positive), penalty=penalty)
+        pl.solver_reset(B, grid / cw, x0=np.concatenate([x0, pad], axis=1))
+    if omega is None:
+        bc = b - b.mean() if fit_intercept else b
+        target = float(GAP_BOUND) * 0.5 * float(bc @ bc)
+    else:
+        bc = b - float(omega @ b) / float(omega.sum()) if fit_intercept else b
+        target = float(GAP_BOUND) * 0.5 * float(omega @ (bc * bc))
+    run = _screened_loop(pl, B, grid / cw, target / cw, ITER_MAX, check_every, shrink, intercept=bool(fit_intercept),
+                         positive=bool(positive), penalty=penalty, weights=weights)
     cert = run["cert"]
     out = dict(x=run["x"][:, :n_given], mus=grid[:n_given].copy(), mu_max=mu_max, iters=run["t"],
                reached=run["reached"][:n_given], first_reached=run["first"][:n_given])
     for key in PanelLasso.GAP_KEYS:
-        out[key] = cert[key][:n_given]
+        out[key] = cert[key][:n_given] * cw if key in _SCALED_KEYS else cert[key][:n_given]
     out["intercept"] = cert["intercept"][:n_given]
     out.update(active=run["active"], compactions=run["compactions"], compact_seconds=run["compact_seconds"])
     return out
@@ -651,7 +729,8 @@ def lasso_path(A, b, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_BOUND=1e-4
 
 def lasso_cv(A, b, n_folds=8, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_BOUND=1e-4, ITER_MAX=4096,
              check_every=PATH_CHECK_EVERY, seed=0, masks=None, refit=True, return_x=False, device=None,
-             shrink=0.0, warm_refit=False, fit_intercept=False, positive=False, penalty_factors=None):
+             shrink=0.0, warm_refit=False, fit_intercept=False, positive=False, penalty_factors=None,
+             sample_weight=None):
     """K-fold cross-validation over a grid of mu as ONE panel on one bound A: column c = f * n_mus + j
     solves fold f (the rows of ``masks[f]``) at ``mus[j]``, min 1/2 ||w_f o (A x - b)||^2 + mu_j ||x||_1,
     through ``PanelLasso.set_row_mask``.  n_folds * n_mus <= 128 and n_folds >= 2 (ValueError
@@ -695,9 +774,17 @@ def lasso_cv(A, b, n_folds=8, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_B
     ``penalty_factors``: an (n,) vector p, every entry finite and > 0 (ValueError
     otherwise), shared by every fold: each column solves its fold with the penalty mu sum_j p_j |x_j|
     (``PanelLasso.set_penalty_factors``); the refit and every narrower context of ``shrink`` get it too.  Used as
-    given, not renormalised.  With ``mus=None`` mu_max is max_j |a_j . b| / p_j."""
+    given, not renormalised.  With ``mus=None`` mu_max is max_j |a_j . b| / p_j.
+
+    ``sample_weight`` (``Block`` must be 1): an (m,) vector omega, finite, >= 0, not all zero
+    (ValueError otherwise), used as given.  Column (f, j) solves min 1/2 sum_i fold_f(i) omega_i e_i^2 + mu_j sum p |x|
+    through ``PanelLasso.set_row_weights`` -- weights fold_f(i) omega_i / c with c = max omega and mu_j / c, scoring
+    weights (1 - fold_f(i)) omega_i -- instead of the row mask; mse is sum h e^2 / sum h per fold, the bound
+    GAP_BOUND * 1/2 sum fold_f omega b^2 (b centred over the fold's weighted mean with ``fit_intercept``), and
+    ``mus``, mu_max and gap are in the caller's scale.  The refit runs with the weights omega / c and no mask."""
     from .cpu_calculation import kfold_masks
     penalty = _check_penalty(penalty_factors, int(A.shape[1]))
+    omega = _check_sample_weight(sample_weight, int(A.shape[0]), Block)
     if int(check_every) <= 0:
         raise ValueError("check_every must be > 0")
     shrink = _check_shrink(shrink)
@@ -733,22 +820,41 @@ def lasso_cv(A, b, n_folds=8, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_B
     if penalty is not None:
         pl.set_penalty_factors(penalty)
     B = np.repeat(b[:, None], k, axis=1)
+    # sample weights: the library solves every column divided by c = max omega; `mus` stays in the caller's scale
+    cw = 1.0 if omega is None else float(omega.max())
+    if omega is not None:
+        pl.set_row_weights(omega / cw)
     if mus is None:
         pl.solver_reset(B, 1.0)
-        mus = _grid_below(float(pl.duality_gap(screen=False)["gnorm_inf"][0]), n_mus, hi, lo, positive)
+        mus = _grid_below(cw * float(pl.duality_gap(screen=False)["gnorm_inf"][0]), n_mus, hi, lo, positive)
     cols = np.concatenate([np.arange(ncol), np.zeros(k - ncol, dtype=np.int64)])   # the pad: copies of column 0
     fold, jmu = cols // n_mus, cols % n_mus
-    pl.set_row_mask(masks[fold].T)
-    pl.solver_reset(B, mus[jmu])
-    def centred(wf, v):   # w o v, or P_w v with the intercept
-        return wf * (v - (wf @ v) / wf.sum()) if fit_intercept else wf * v
-    bb = np.array([float(centred(masks[f].astype(np.float64), b) @ centred(masks[f].astype(np.float64), b))
-                   for f in range(n_folds)])
-    run = _screened_loop(pl, B, mus[jmu], float(GAP_BOUND) * 0.5 * bb[fold], ITER_MAX, check_every, shrink,
-                         mask=masks[fold].T, intercept=fit_intercept, positive=positive, penalty=penalty)
+    if omega is None:
+        weights = None
+        pl.set_row_mask(masks[fold].T)
+        def centred(wf, v):   # w o v, or P_w v with the intercept
+            return wf * (v - (wf @ v) / wf.sum()) if fit_intercept else wf * v
+        bb = np.array([float(centred(masks[f].astype(np.float64), b) @ centred(masks[f].astype(np.float64), b))
+                       for f in range(n_folds)])
+        count = (masks == 0).sum(axis=1).astype(np.float64)
+    else:
+        wf = masks.astype(np.float64) * omega                     # (n_folds, m): the fold's training weights
+        hf = (1.0 - masks.astype(np.float64)) * omega             # ... and its scoring weights
+        if not np.all(wf.sum(axis=1) > 0.0):
+            raise ValueError("sample_weight leaves a fold without a training row of positive weight")
+        weights = (np.ascontiguousarray((wf / cw)[fold].T), np.ascontiguousarray(hf[fold].T))
+        pl.set_row_weights(*weights)
+        def wss(wv, v):   # sum w v^2, v centred over the weighted mean with the intercept
+            vc = v - (wv @ v) / wv.sum() if fit_intercept else v
+            return float(wv @ (vc * vc))
+        bb = np.array([wss(wf[f], b) for f in range(n_folds)])
+        count = hf.sum(axis=1)
+    pl.solver_reset(B, mus[jmu] / cw)
+    run = _screened_loop(pl, B, mus[jmu] / cw, float(GAP_BOUND) * 0.5 * bb[fold] / cw, ITER_MAX, check_every, shrink,
+                         mask=None if omega is not None else masks[fold].T, intercept=fit_intercept, positive=positive,
+                         penalty=penalty, weights=weights)
     t, cert = run["t"], run["cert"]
     shape = (n_folds, n_mus)
-    count = (masks == 0).sum(axis=1).astype(np.float64)
     mse = cert["holdout_sse"][:ncol].reshape(shape) / count[:, None]
     mean_mse = mse.mean(axis=0)
     se_mse = mse.std(axis=0, ddof=1) / np.sqrt(n_folds)
@@ -757,7 +863,7 @@ def lasso_cv(A, b, n_folds=8, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_B
     out = dict(mus=mus.copy(), mse=mse, mean_mse=mean_mse, se_mse=se_mse, best=best,
                best_1se=int(within[np.argmax(mus[within])]), iters=t,
                reached=run["reached"][:ncol].reshape(shape),
-               gap=cert["gap"][:ncol].reshape(shape), n_keep=cert["n_keep"][:ncol].reshape(shape), masks=masks,
+               gap=cert["gap"][:ncol].reshape(shape) * cw, n_keep=cert["n_keep"][:ncol].reshape(shape), masks=masks,
                active=run["active"], compactions=run["compactions"], compact_seconds=run["compact_seconds"])
     if fit_intercept:
         out["intercept_folds"] = cert["intercept"][:ncol].reshape(shape)
@@ -765,17 +871,27 @@ def lasso_cv(A, b, n_folds=8, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_B
         out["x_folds"] = run["x"][:, :ncol].reshape(-1, n_folds, n_mus)
     if refit:
         grid = np.concatenate([mus, np.full(k - n_mus, mus.max())])   # pad_mus' layout at this panel's width
-        pl.set_row_mask(None)
+        if omega is None:
+            pl.set_row_mask(None)
+            rweights = None
+        else:   # the full-data weights, no mask
+            rweights = (omega / cw, None)
+            pl.set_row_weights(*rweights)
         if warm_refit:   # each mu from the mean of its fold solutions; the pad takes the largest mu's column
             xm = run["x"][:, :ncol].reshape(-1, n_folds, n_mus).mean(axis=1)
             xm = np.concatenate([xm, np.repeat(xm[:, [int(np.argmax(mus))]], k - n_mus, axis=1)], axis=1)
-            pl.solver_reset(B, grid, x0=xm)
+            pl.solver_reset(B, grid / cw, x0=xm)
         else:
-            pl.solver_reset(B, grid)
-        bc = b - b.mean() if fit_intercept else b
-        rrun = _screened_loop(pl, B, grid, float(GAP_BOUND) * 0.5 * float(bc @ bc), ITER_MAX, check_every, shrink,
-                              intercept=fit_intercept, positive=positive, penalty=penalty)
-        out.update(x=rrun["x"][:, :n_mus], refit_gap=rrun["cert"]["gap"][:n_mus], refit_iters=rrun["t"],
+            pl.solver_reset(B, grid / cw)
+        if omega is None:
+            bc = b - b.mean() if fit_intercept else b
+            rtarget = float(GAP_BOUND) * 0.5 * float(bc @ bc)
+        else:
+            bc = b - float(omega @ b) / float(omega.sum()) if fit_intercept else b
+            rtarget = float(GAP_BOUND) * 0.5 * float(omega @ (bc * bc))
+        rrun = _screened_loop(pl, B, grid / cw, rtarget / cw, ITER_MAX, check_every, shrink,
+                              intercept=fit_intercept, positive=positive, penalty=penalty, weights=rweights)
+        out.update(x=rrun["x"][:, :n_mus], refit_gap=rrun["cert"]["gap"][:n_mus] * cw, refit_iters=rrun["t"],
                    refit_compactions=rrun["compactions"])
         if fit_intercept:
             out["intercept"] = rrun["cert"]["intercept"][:n_mus]

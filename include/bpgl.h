@@ -101,7 +101,14 @@ const char* bpgl_last_error(void);
  *                second copy) and the panel tuning key "penalty" (bpgl_panel_get_tuning
  *                only).  Opt-in: with it off every kernel that existed is unchanged, bit for bit, and a vector
  *                of ones gives the same bits as off.  bpgl_panel_scratch_bytes grows by the factors' piece, laid
- *                out after everything that existed (8 n + 256 bytes). */
+ *                out after everything that existed (8 n + 256 bytes).
+ *   310 (0.3.10): + bpgl_panel_set_row_weights (observation weights w_i in [0, 1] per right-hand side, glmnet's
+ *                weights / scikit-learn's sample_weight, and scoring weights for out[8 k + 7]; on the A that is
+ *                bound -- no row-rescaled copy; one feature block with the deferred x update)
+ *                and the panel tuning key "row_weights" (bpgl_panel_get_tuning only).  Opt-in: with it off every
+ *                kernel that existed is unchanged, bit for bit, and 0/1 weights compute what the row mask
+ *                computes.  bpgl_panel_scratch_bytes grows by the weights' pieces, laid out after everything that
+ *                existed (24 nrhs m + 256 bytes). */
 int bpgl_version(void);
 
 /*
@@ -600,6 +607,45 @@ int bpgl_panel_set_positive(bpgl_panel* ctx, int on);
  * Legal any time after bpgl_panel_bind (BPGL_E_STATE before it; BPGL_E_ARG on a null context).
  */
 int bpgl_panel_set_penalty(bpgl_panel* ctx, const double* pen);
+/*
+ * Observation weights (since ABI 310): with `wt` non-NULL right-hand side k solves
+ *   min 1/2 sum_i w_ki (a_i . x - b_ki)^2 + mu_k sum_j p_j |x_j|
+ * (with the intercept's profiling -- then over the weighted mean --, x >= 0 and / or the penalty factors when those
+ * are installed).  wt: device fp64 [nrhs][m], every entry finite and in [0, 1] (scale larger weights by their
+ * maximum c and pass mu / c: the minimiser is the same).  hold: device fp64 [nrhs][m] or NULL, every entry finite
+ * and >= 0: the scoring weights h of out[8 k + 7] = sum_i h_ki e_ki^2, e = a_i . x_k - b_ki (+ beta0 with the
+ * intercept); NULL means h = 1 where wt is 0 and 0 elsewhere, the row mask's rule.  A validation kernel reads both
+ * (one readback: a set-up call) and BPGL_E_ARG is returned, with nothing changed -- whatever was installed before
+ * stays in force -- when an entry is out of range.  Both are copied into the context's scratch and the call
+ * returns when the copies are done, so the caller's buffers are free after it.  wt == NULL clears the weights
+ * (`hold` is then ignored).
+ * Weights and a row mask are alternatives and the last call wins: bpgl_panel_set_row_mask clears the weights, and
+ * this call (also with wt == NULL) clears a caller's mask.  The order of this call and bpgl_panel_set_intercept does
+ * not matter; with the intercept n_w = sum_i w_ki (fp64, fixed order) stands where the in-row count stood and every
+ * mean is the weighted one.  bpgl_panel_diag still returns the diag in effect, over all rows: d_j >= sum_i w_i a_ij^2
+ * because w <= 1, so the step and the screen stay safe.
+ * What the solver carries is R^ = w o (A x - b) (bpgl_panel_residual; exactly 0 at the zero-weight rows from the
+ * reset on), the stored B is w o B, pass 1 and pass 2 are the unchanged kernels, and the fold differs:
+ *   fold          s^ = w o s
+ *   line search   rs = sum_i R^_i s_i (the UNWEIGHTED s), ss = sum_i s_i s^_i; gamma = clip(-(rs + mu (sbx - sx)) / ss, 0, 1),
+ *                 0 when ss = 0; with the intercept sm = sum s^, c = sm / n_w, curvature ss - c sm
+ *   update        R^ += gamma s^ (with the intercept gamma (s^ - c w)); the carried operand takes the same step
+ *   certificate   R_fresh = w o e (w o (e - ebar_w) with the intercept) and G = A^T R_fresh; primal = 1/2 sum w e^2 +
+ *                 mu sum p |x|, dual = -1/2 s^2 sum w e^2 - s sum w e b, both sums formed from e where a_i . x is at
+ *                 hand, never by dividing R_fresh by w; scale, gap, out[8 k + 4] and the screen as without weights;
+ *                 drift = max |R^ - R_fresh|; beta0 = -sum w e / n_w
+ * With every w in {0, 1} each of these is, term for term, what the row mask computes.  A right-hand side whose
+ * weights are all 0 takes no steps and reports zeros.
+ * One feature block with the deferred x update: with weights installed bpgl_panel_reset and bpgl_panel_reset_x0
+ * return BPGL_E_STATE for nblock > 1 and for the tuning key defer_x = 0.  bpgl_panel_reset_x0 starts at
+ * R^ = w o (A X0 - B) (centred with the intercept) through the certificate's product 1.
+ * It invalidates the solver and drops the graphs exactly as bpgl_panel_set_row_mask does, and repeats the fused
+ * update's occupancy check for the variant that will run; bpgl_panel_bind switches the weights off.
+ * bpgl_panel_get_tuning("row_weights") reports them.  bpgl_panel_gather_columns, bpgl_panel_mm and bpgl_panel_mtm
+ * are unaffected.  With it off every result is bitwise what ABI 309 computes.
+ * Legal any time after bpgl_panel_bind (BPGL_E_STATE before it; BPGL_E_ARG on a null context).
+ */
+int bpgl_panel_set_row_weights(bpgl_panel* ctx, const double* wt, const double* hold);
 /*
  * Warm start (since ABI 306): bpgl_panel_reset at a given iterate.
  * X0: device fp32 [nblock][nrhs][w] (the layout of bpgl_panel_x), 16-byte aligned, caller-owned.
