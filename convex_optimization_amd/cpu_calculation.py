@@ -21,11 +21,12 @@ numpy fp64 restatement of the device's optimality certificate and screening rule
 of a regularization path; ``kfold_masks``, ``masked_panel_iterate`` and ``masked_duality_gap``, the
 restatement of the panel's row-masked problems (K-fold cross-validation, DESIGN.md section 11);
 ``compaction_columns``, the columns a screened panel keeps when it is compacted (DESIGN.md section 12);
-``centred_diag``, ``intercept_panel_iterate`` and ``intercept_duality_gap``, the restatement of the
-panel's intercept; ``positive_panel_iterate`` and ``positive_duality_gap``, the
-restatement of the panel's non-negative lasso (x >= 0); ``penalty_panel_iterate`` and
-``penalty_duality_gap``, the restatement of the panel's penalty factors (per-column l1 weights, DESIGN.md
-section 15).
+``centred_diag`` and the ``intercept_*``, ``positive_*``, ``penalty_*`` and ``weighted_*`` pairs
+``*_panel_iterate`` / ``*_duality_gap``: the panel's intercept, non-negative lasso (x >= 0), penalty factors
+(per-column l1 weights) and observation weights (DESIGN.md sections 13-16).  Those pairs and
+``masked_duality_gap`` are thin wrappers of ONE statement of the iteration and ONE of the certificate,
+``_panel_iterate`` and ``_panel_gap``; ``masked_panel_iterate`` alone stands beside them,
+pinned bitwise to the C oracle.
 """
 import numpy as np
 
@@ -159,6 +160,8 @@ def masked_panel_iterate(A, b, w, mu, Block, iters, diag=None, x0=None):
     x^ = S(x - G / d, mu / d), D = x^ - x, S = w o (A_m D), the exact line search along D and
     x += gamma D.  ``diag``: the d_j > 0 of the shrink, (n,); default the FULL column norms ||a_j||^2,
     as the device uses (not those of the masked rows).  Returns dict(x, r) with r the masked residual."""
+    # Not a wrapper of _panel_iterate: it carries A x per block and forms r = sum Ax - w b, the reference's own order,
+    # and tests/test_panel_cv_host.py::test_all_ones_mask_is_the_numpy_oracle_bitwise pins its bits to oracle.run_numpy.
     A = np.asarray(A, dtype=np.float64)
     m, n = A.shape
     Block = int(Block)
@@ -189,209 +192,42 @@ def masked_panel_iterate(A, b, w, mu, Block, iters, diag=None, x0=None):
 
 
 def masked_duality_gap(A, b, w, x, mu, diag=None):
-    """The certificate of ``duality_gap`` on the masked problem: r = w o (A x - b), g = A^T r, and
-    primal, dual, gap, scale, gnorm_inf from them (b enters through r . b, where the held-out rows
-    of r are 0).  Also holdout_sse = sum (1 - w)(A x - b)^2, and the gap-safe score and keep with
-    ``diag`` (default the FULL column norms: d_j >= ||w o a_j||^2, so the rule stays safe)."""
-    A = np.asarray(A, dtype=np.float64)
-    b = np.asarray(b, dtype=np.float64).reshape(-1)
-    x = np.asarray(x, dtype=np.float64).reshape(-1)
-    w = (np.asarray(w).reshape(-1) != 0).astype(np.float64)
-    mu = float(mu)
-    e = A @ x - b
-    r = w * e
-    g = A.T @ r
-    rr = float(r @ r)
-    primal = 0.5 * rr + mu * float(np.abs(x).sum())
-    gn = float(np.max(np.abs(g)))
-    scale = min(1.0, mu / gn) if gn > 0.0 else 1.0
-    dual = -0.5 * scale * scale * rr - scale * float(r @ b)
-    gap = primal - dual
-    h = (1.0 - w) * e
-    dg = np.square(A).sum(axis=0) if diag is None else np.asarray(diag, dtype=np.float64).reshape(-1)
-    score = scale * np.abs(g) + np.sqrt(dg) * np.sqrt(2.0 * np.maximum(gap, 0.0))
-    return dict(primal=primal, dual=dual, gap=gap, scale=scale, gnorm_inf=gn, holdout_sse=float(h @ h),
-                score=score, keep=~(score < mu), g=g, r=r)
+    """The certificate of ``duality_gap`` on the masked problem (0/1 row weights ``w``): ``_panel_gap`` with no
+    factors, no intercept and no sign constraint.  ``diag``: default the FULL column norms (d_j >= ||w o a_j||^2, so
+    the rule stays safe)."""
+    return _panel_gap(A, b, _rows01(w, A), x, mu, None, diag, False, False, None)
 
 
 # ---------------------------------------------------------------------------
-# Intercept (DESIGN.md section 13): min over x, beta0 of 1/2 || w o (A x + beta0 - b) ||^2 + mu ||x||_1.
-# beta0 is profiled out: the objective is 1/2 || P_w (A x - b) ||^2 + mu ||x||_1 with
-# P_w v = w o (v - (w . v) / n_w), and the iteration carries the centred residual.  The host restatement
-# of bpgl_panel_set_intercept's solver and certificate.
+# One fp64 restatement of every panel mode (DESIGN.md section 17; the modes: sections 11, 13-16):
+#   min over x (and beta0 with ``intercept``) of 1/2 sum_i w_i (a_i . x + beta0 - b_i)^2 + mu sum_j p_j |x_j|,
+#   x >= 0 with ``positive``, with w_i in [0, 1] (0/1: a row mask) and p_j > 0.
+# beta0 is profiled out: the residual is centred over its weighted mean and the iteration carries the centred one.
+# ``_panel_iterate`` and ``_panel_gap`` state the device's solver and certificate once; the public names below fix a
+# mode's flags and validate its arguments.
 # ---------------------------------------------------------------------------
-def _centre(w, v):
-    """P_w v = w o (v - mean of v over the rows with w = 1); 0 when w has no such row."""
-    nw = float(w.sum())
-    return w * (v - (float(w @ v) / nw if nw > 0 else 0.0))
-
-
 def centred_diag(A):
     """d_j = sum_i (a_ij - mean_j)^2 over all rows, (n,): the diag of the intercept's shrink and screen.
-    d_j >= || P_w a_j ||^2 for every 0/1 w, so one d serves every fold.  The deviations are taken from
+    d_j >= || P_w a_j ||^2 for every w in [0, 1], so one d serves every fold.  The deviations are taken from
     the column's first entry, so a constant column gives exactly 0."""
     A = np.asarray(A, dtype=np.float64)
     dev = A - A[:1]
     return np.square(dev - dev.sum(axis=0) / A.shape[0]).sum(axis=0)
 
 
-def intercept_panel_iterate(A, b, w, mu, iters, diag=None, x0=None):
-    """``iters`` updates (one feature block) of the panel's iteration with the intercept on one
-    right-hand side, in fp64: R = P_w (A x - b), G = A^T R, the shrink with ``diag`` (default
-    ``centred_diag(A)``; a column with d_j = 0 keeps x_j = 0), S = w o (A D), c = sum S / n_w, the exact
-    line search gamma = clip(-(R.S + mu (|x + D|_1 - |x|_1)) / (S.S - c sum S), 0, 1) (0 when the
-    curvature is <= 0), x += gamma D and R += gamma w o (S - c).  Returns dict(x, r, intercept) with
-    intercept = -mean over the in-rows of (A x - b)."""
-    A = np.asarray(A, dtype=np.float64)
-    n = A.shape[1]
-    b = np.asarray(b, dtype=np.float64).reshape(-1)
-    w = (np.asarray(w).reshape(-1) != 0).astype(np.float64)
-    nw = float(w.sum())
-    mu = float(mu)
-    dg = centred_diag(A) if diag is None else np.asarray(diag, dtype=np.float64).reshape(-1)
-    with np.errstate(divide="ignore"):
-        rec = np.where(dg > 0, 1.0 / dg, 0.0)
-    x = np.zeros(n) if x0 is None else np.array(x0, dtype=np.float64).reshape(-1)
-    R = _centre(w, A @ x - b)
-    for _ in range(int(iters)):
-        g = A.T @ R
-        rx = dg * x - g
-        Bx = rec * (np.sign(rx) * np.maximum(np.abs(rx) - mu, 0))
-        D = Bx - x
-        s = w * (A @ D)
-        sm = float(s.sum())
-        c = sm / nw if nw > 0 else 0.0
-        r1 = R @ s + mu * (np.abs(Bx).sum() - np.abs(x).sum())
-        r2 = s @ s - c * sm
-        gamma = 0.0 if r2 <= 0 else float(np.clip(-r1 / r2, 0, 1))
-        x += gamma * D
-        R += gamma * w * (s - c)
-    e = A @ x - b
-    return dict(x=x, r=R, intercept=-(float(w @ e) / nw) if nw > 0 else 0.0)
+def _diag_in_effect(A, diag, intercept):
+    """``diag`` as given; otherwise ``centred_diag(A)`` with ``intercept``, else the FULL column norms ||a_j||^2 (not
+    those of the weighted rows: d_j >= sum_i w_i a_ij^2 because w <= 1), as the device uses."""
+    if diag is not None:
+        return np.asarray(diag, dtype=np.float64).reshape(-1)
+    return centred_diag(A) if intercept else np.square(A).sum(axis=0)
 
 
-def intercept_duality_gap(A, b, w, x, mu, diag=None):
-    """``masked_duality_gap`` on the profiled problem: with e = A x - b and c = the in-row mean of e,
-    r = w o (e - c) (it sums to zero over the in-rows: the intercept's dual constraint), g = A^T r,
-    primal, dual, gap, scale, gnorm_inf from them; intercept = -c; holdout_sse = the held-out sum of
-    (a_i . x + intercept - b_i)^2; score and keep with ``diag`` (default ``centred_diag(A)``)."""
-    A = np.asarray(A, dtype=np.float64)
-    b = np.asarray(b, dtype=np.float64).reshape(-1)
-    x = np.asarray(x, dtype=np.float64).reshape(-1)
-    w = (np.asarray(w).reshape(-1) != 0).astype(np.float64)
-    nw = float(w.sum())
-    mu = float(mu)
-    e = A @ x - b
-    c = float(w @ e) / nw if nw > 0 else 0.0
-    r = w * (e - c)
-    g = A.T @ r
-    rr = float(r @ r)
-    primal = 0.5 * rr + mu * float(np.abs(x).sum())
-    gn = float(np.max(np.abs(g)))
-    scale = min(1.0, mu / gn) if gn > 0.0 else 1.0
-    dual = -0.5 * scale * scale * rr - scale * float(r @ b)
-    gap = primal - dual
-    h = (1.0 - w) * (e - c)
-    dg = centred_diag(A) if diag is None else np.asarray(diag, dtype=np.float64).reshape(-1)
-    score = scale * np.abs(g) + np.sqrt(dg) * np.sqrt(2.0 * np.maximum(gap, 0.0))
-    return dict(primal=primal, dual=dual, gap=gap, scale=scale, gnorm_inf=gn, holdout_sse=float(h @ h),
-                intercept=-c if nw > 0 else 0.0, score=score, keep=~(score < mu), g=g, r=r)
+def _rows01(w, A):
+    """A row mask as fp64 0/1; None: all rows."""
+    return np.ones(np.shape(A)[0]) if w is None else (np.asarray(w).reshape(-1) != 0).astype(np.float64)
 
 
-# ---------------------------------------------------------------------------
-# Non-negative lasso (DESIGN.md section 14): min 1/2 || w o (A x - b) ||^2 + mu sum_j x_j subject to x >= 0,
-# with or without the intercept's profiling.  The host restatement of bpgl_panel_set_positive's solver and
-# certificate.
-# ---------------------------------------------------------------------------
-def positive_panel_iterate(A, b, w, mu, Block, iters, diag=None, x0=None, intercept=False):
-    """``iters`` block updates (cyclic over ``Block`` feature blocks; ``intercept`` needs Block = 1) of the
-    panel's iteration on the non-negative problem of one right-hand side, in fp64: R = w o (A x - b)
-    (P_w (A x - b) with ``intercept``), G = A_m^T R, the one-sided prox x^ = max(0, S(d x - G, mu) / d)
-    (x^ = 0 where d = 0), D = x^ - x, S = w o (A_m D), the exact line search along D (curvature |P_w S|^2
-    with ``intercept``) and x += gamma D.  ``w`` None: all rows.  ``diag``: default the full column norms
-    (``centred_diag(A)`` with ``intercept``).  ``x0`` is projected to max(x0, 0).  Returns dict(x, r[,
-    intercept]); x >= 0 at every iteration."""
-    A = np.asarray(A, dtype=np.float64)
-    m, n = A.shape
-    Block = int(Block)
-    if intercept and Block != 1:
-        raise ValueError("intercept needs Block = 1")
-    wd = n // Block
-    b = np.asarray(b, dtype=np.float64).reshape(-1)
-    w = np.ones(m) if w is None else (np.asarray(w).reshape(-1) != 0).astype(np.float64)
-    nw = float(w.sum())
-    mu = float(mu)
-    if diag is None:
-        dg = centred_diag(A) if intercept else np.square(A).sum(axis=0)
-    else:
-        dg = np.asarray(diag, dtype=np.float64).reshape(-1)
-    with np.errstate(divide="ignore"):
-        rec = np.where(dg > 0, 1.0 / np.where(dg > 0, dg, 1.0), 0.0).reshape(Block, wd)
-    dg = dg.reshape(Block, wd)
-    x = np.maximum(np.zeros(n) if x0 is None else np.array(x0, dtype=np.float64).reshape(-1), 0.0).reshape(Block, wd)
-    proj = (lambda v: _centre(w, v)) if intercept else (lambda v: w * v)
-    R = proj(A @ x.reshape(-1) - b)
-    for t in range(int(iters)):
-        mb = t % Block
-        Am = A[:, mb * wd:(mb + 1) * wd]
-        g = Am.T @ R
-        rx = dg[mb] * x[mb] - g
-        Bx = np.maximum(rec[mb] * (np.sign(rx) * np.maximum(np.abs(rx) - mu, 0)), 0.0)
-        D = Bx - x[mb]
-        s = w * (Am @ D)
-        ps = proj(Am @ D)
-        r1 = R @ s + mu * D.sum()          # |x + D|_1 - |x|_1 on the feasible set, without the cancellation
-        r2 = ps @ ps
-        gamma = 0.0 if r2 <= 0 else float(np.clip(-r1 / r2, 0, 1))
-        x[mb] = x[mb] + gamma * D          # >= 0: D >= -x and gamma <= 1, each rounding monotone
-        R = R + gamma * ps
-    out = dict(x=x.reshape(-1), r=R)
-    if intercept:
-        e = A @ out["x"] - b
-        out["intercept"] = -(float(w @ e) / nw) if nw > 0 else 0.0
-    return out
-
-
-def positive_duality_gap(A, b, w, x, mu, diag=None, intercept=False):
-    """The certificate of the non-negative problem at a feasible x: r = w o (A x - b) (P_w (A x - b) with
-    ``intercept``), g = A^T r.  The dual constraint is one-sided, -a_j . theta <= mu, so gnorm_inf is
-    max_j (-g_j)+, scale = min(1, mu / that) (1 when it is 0) makes scale r dual feasible, and primal =
-    1/2 |r|^2 + mu sum |x|, dual = -1/2 scale^2 |r|^2 - scale r.b, gap = primal - dual >= P(x) - P* as in
-    ``masked_duality_gap``.  The gap-safe score is scale (-g_j) + sqrt(d_j) sqrt(2 max(gap, 0)), keep =
-    not (score < mu): a column that is not kept is 0 at every optimum.  ``w`` None: all rows; ``diag``: default
-    the full column norms (``centred_diag(A)`` with ``intercept``).  Also holdout_sse and intercept as in
-    ``masked_duality_gap`` / ``intercept_duality_gap``."""
-    A = np.asarray(A, dtype=np.float64)
-    b = np.asarray(b, dtype=np.float64).reshape(-1)
-    x = np.asarray(x, dtype=np.float64).reshape(-1)
-    w = np.ones(A.shape[0]) if w is None else (np.asarray(w).reshape(-1) != 0).astype(np.float64)
-    nw = float(w.sum())
-    mu = float(mu)
-    e = A @ x - b
-    c = (float(w @ e) / nw if nw > 0 else 0.0) if intercept else 0.0
-    r = w * (e - c)
-    g = A.T @ r
-    rr = float(r @ r)
-    primal = 0.5 * rr + mu * float(np.abs(x).sum())
-    gn = float(np.max(np.where(g > 0, 0.0, -g)))       # NaN propagates
-    scale = min(1.0, mu / gn) if gn > 0.0 else 1.0
-    dual = -0.5 * scale * scale * rr - scale * float(r @ b)
-    gap = primal - dual
-    h = (1.0 - w) * (e - c)
-    if diag is None:
-        dg = centred_diag(A) if intercept else np.square(A).sum(axis=0)
-    else:
-        dg = np.asarray(diag, dtype=np.float64).reshape(-1)
-    score = scale * (-g) + np.sqrt(dg) * np.sqrt(2.0 * np.maximum(gap, 0.0))
-    return dict(primal=primal, dual=dual, gap=gap, scale=scale, gnorm_inf=gn, holdout_sse=float(h @ h),
-                intercept=-c if (intercept and nw > 0) else 0.0, score=score, keep=~(score < mu), g=g, r=r)
-
-
-# ---------------------------------------------------------------------------
-# Penalty factors (DESIGN.md section 15): min 1/2 || w o (A x - b) ||^2 + mu sum_j p_j |x_j| with p_j > 0, with or
-# without the intercept's profiling and the sign constraint.  The host restatement of bpgl_panel_set_penalty's
-# solver and certificate.  The factors are used as given (no renormalisation to sum p = n).
-# ---------------------------------------------------------------------------
 def _penalty(p, n):
     p = np.asarray(p, dtype=np.float64).reshape(-1)
     if p.size != n or not np.all(np.isfinite(p) & (p > 0.0)):
@@ -399,30 +235,43 @@ def _penalty(p, n):
     return p
 
 
-def penalty_panel_iterate(A, b, w, mu, p, Block, iters, diag=None, x0=None, intercept=False, positive=False):
-    """``iters`` block updates (cyclic over ``Block`` feature blocks; ``intercept`` needs Block = 1) of the
-    panel's iteration on the weighted problem of one right-hand side, in fp64: R = w o (A x - b) (P_w (A x - b)
-    with ``intercept``), G = A_m^T R, the prox x^_j = S(d_j x_j - G_j, mu p_j) / d_j (max(0, .) with ``positive``;
-    0 where d_j = 0), D = x^ - x, S = w o (A_m D), the exact line search of the weighted objective along D,
-    gamma = clip(-(R.S + mu (sum p |x + D| - sum p |x|)) / |P S|^2, 0, 1), and x += gamma D.  ``p``: (n,), every
-    entry finite and > 0 (ValueError otherwise).  ``w`` None: all rows.  ``diag``: default the full column norms
-    (``centred_diag(A)`` with ``intercept``).  With ``positive`` ``x0`` is projected to max(x0, 0).  Returns
-    dict(x, r[, intercept])."""
+def _row_weights(w, m):
+    w = np.asarray(w, dtype=np.float64).reshape(-1)
+    if w.size != m or not np.all(np.isfinite(w) & (w >= 0.0) & (w <= 1.0)):
+        raise ValueError("row weights: m entries, each finite and in [0, 1]")
+    return w
+
+
+def _wmean(w, v):
+    """sum w v / sum w; 0 when sum w = 0."""
+    nw = float(w.sum())
+    return float(w @ v) / nw if nw > 0 else 0.0
+
+
+def _panel_iterate(A, b, w, mu, p, Block, iters, diag, x0, intercept, positive):
+    """``iters`` block updates (cyclic over ``Block`` feature blocks; ``intercept`` needs Block = 1, ValueError
+    otherwise) of the panel's iteration on one right-hand side, in fp64.  ``w``: fp64 (m,) in [0, 1]; ``p``: None (all
+    ones) or validated factors; ``diag``: see ``_diag_in_effect``.
+
+    The carried residual is R = w o (A x - b), or w o (e - ebar_w) with ``intercept`` (ebar_w the weighted mean of
+    e = A x - b).  Per update of block m: g = A_m^T R; the prox x^_j = S(d_j x_j - g_j, mu p_j) / d_j (max(0, .) with
+    ``positive``; a column with d_j = 0 keeps x_j = 0); D = x^ - x_m; s = A_m D and s^ = w o s; c = sum s^ / sum w
+    under ``intercept`` and 0 otherwise; the exact line search of the objective along D,
+    gamma = clip(-(R . s + mu sum_j p_j (|x_j + D_j| - |x_j|)) / (s . s^ - c sum s^), 0, 1), 0 when the curvature is
+    <= 0; x_m += gamma D and R += gamma (s^ - c w).  With ``positive`` ``x0`` is projected to max(x0, 0), and x >= 0 at
+    every iteration (D >= -x and gamma <= 1, each rounding monotone).  Returns dict(x, r = R[, intercept =
+    -sum w (A x - b) / sum w])."""
     A = np.asarray(A, dtype=np.float64)
-    m, n = A.shape
+    n = A.shape[1]
     Block = int(Block)
     if intercept and Block != 1:
         raise ValueError("intercept needs Block = 1")
     wd = n // Block
     b = np.asarray(b, dtype=np.float64).reshape(-1)
-    w = np.ones(m) if w is None else (np.asarray(w).reshape(-1) != 0).astype(np.float64)
     nw = float(w.sum())
     mu = float(mu)
-    pw = _penalty(p, n).reshape(Block, wd)
-    if diag is None:
-        dg = centred_diag(A) if intercept else np.square(A).sum(axis=0)
-    else:
-        dg = np.asarray(diag, dtype=np.float64).reshape(-1)
+    pw = (np.ones(n) if p is None else p).reshape(Block, wd)
+    dg = _diag_in_effect(A, diag, intercept)
     with np.errstate(divide="ignore"):
         rec = np.where(dg > 0, 1.0 / np.where(dg > 0, dg, 1.0), 0.0).reshape(Block, wd)
     dg = dg.reshape(Block, wd)
@@ -430,8 +279,8 @@ def penalty_panel_iterate(A, b, w, mu, p, Block, iters, diag=None, x0=None, inte
     if positive:
         x = np.maximum(x, 0.0)
     x = x.reshape(Block, wd).copy()
-    proj = (lambda v: _centre(w, v)) if intercept else (lambda v: w * v)
-    R = proj(A @ x.reshape(-1) - b)
+    e = A @ x.reshape(-1) - b
+    R = w * (e - _wmean(w, e) if intercept else e)
     for t in range(int(iters)):
         mb = t % Block
         Am = A[:, mb * wd:(mb + 1) * wd]
@@ -441,151 +290,45 @@ def penalty_panel_iterate(A, b, w, mu, p, Block, iters, diag=None, x0=None, inte
         if positive:
             Bx = np.maximum(Bx, 0.0)
         D = Bx - x[mb]
-        s = w * (Am @ D)
-        ps = proj(Am @ D)
+        s = Am @ D
+        sh = w * s
+        sm = float(sh.sum())
+        c = (sm / nw if nw > 0 else 0.0) if intercept else 0.0
         # sum p (|x + D| - |x|) coordinate by coordinate, sign(x) D where the step keeps the sign: the two sums'
         # difference would lose the O(|D|^2) that is left of r1 near the optimum
         l1d = np.where(x[mb] * Bx > 0, np.sign(x[mb]) * D, np.abs(Bx) - np.abs(x[mb]))
         r1 = R @ s + mu * float(pw[mb] @ l1d)
-        r2 = ps @ ps
-        gamma = 0.0 if r2 <= 0 else float(np.clip(-r1 / r2, 0, 1))
-        x[mb] = x[mb] + gamma * D
-        R = R + gamma * ps
-    out = dict(x=x.reshape(-1), r=R)
-    if intercept:
-        e = A @ out["x"] - b
-        out["intercept"] = -(float(w @ e) / nw) if nw > 0 else 0.0
-    return out
-
-
-def penalty_duality_gap(A, b, w, x, mu, p, diag=None, intercept=False, positive=False):
-    """The certificate of the weighted problem at x (x >= 0 with ``positive``): r = w o (A x - b) (P_w (A x - b)
-    with ``intercept``), g = A^T r.  The dual constraint is |a_j . theta| <= mu p_j (-a_j . theta <= mu p_j with
-    ``positive``), so gnorm_inf is max_j |g_j| / p_j (max_j (-g_j)+ / p_j), scale = min(1, mu / that) (1 when it
-    is 0) makes scale r dual feasible, and primal = 1/2 |r|^2 + mu sum p_j |x_j|, dual = -1/2 scale^2 |r|^2 -
-    scale r.b, gap = primal - dual.  At x = 0 gnorm_inf is mu_max = max_j |a_j . b| / p_j.  The gap-safe score is
-    scale |g_j| + sqrt(d_j) sqrt(2 max(gap, 0)) (-g_j for |g_j| with ``positive``), keep_j = not (score_j <
-    mu p_j).  ``w`` None: all rows; ``diag``: default the full column norms (``centred_diag(A)`` with
-    ``intercept``).  Also holdout_sse and intercept as in ``masked_duality_gap`` / ``intercept_duality_gap``."""
-    A = np.asarray(A, dtype=np.float64)
-    b = np.asarray(b, dtype=np.float64).reshape(-1)
-    x = np.asarray(x, dtype=np.float64).reshape(-1)
-    w = np.ones(A.shape[0]) if w is None else (np.asarray(w).reshape(-1) != 0).astype(np.float64)
-    nw = float(w.sum())
-    mu = float(mu)
-    p = _penalty(p, A.shape[1])
-    e = A @ x - b
-    c = (float(w @ e) / nw if nw > 0 else 0.0) if intercept else 0.0
-    r = w * (e - c)
-    g = A.T @ r
-    rr = float(r @ r)
-    primal = 0.5 * rr + mu * float(p @ np.abs(x))
-    ga = np.where(g > 0, 0.0, -g) if positive else np.abs(g)
-    gn = float(np.max(ga / p))       # NaN propagates
-    scale = min(1.0, mu / gn) if gn > 0.0 else 1.0
-    dual = -0.5 * scale * scale * rr - scale * float(r @ b)
-    gap = primal - dual
-    h = (1.0 - w) * (e - c)
-    if diag is None:
-        dg = centred_diag(A) if intercept else np.square(A).sum(axis=0)
-    else:
-        dg = np.asarray(diag, dtype=np.float64).reshape(-1)
-    score = scale * (-g if positive else np.abs(g)) + np.sqrt(dg) * np.sqrt(2.0 * np.maximum(gap, 0.0))
-    return dict(primal=primal, dual=dual, gap=gap, scale=scale, gnorm_inf=gn, holdout_sse=float(h @ h),
-                intercept=-c if (intercept and nw > 0) else 0.0, score=score, keep=~(score < mu * p), g=g, r=r)
-
-
-# ---------------------------------------------------------------------------
-# Observation weights (DESIGN.md section 16): min 1/2 sum_i w_i (a_i . x - b_i)^2 + mu sum_j p_j |x_j| with
-# w_i in [0, 1], with or without the intercept's profiling (then over the weighted mean), the sign constraint and the
-# penalty factors.  The host restatement of bpgl_panel_set_row_weights' solver and certificate; one feature block.
-# ---------------------------------------------------------------------------
-def _row_weights(w, m):
-    w = np.asarray(w, dtype=np.float64).reshape(-1)
-    if w.size != m or not np.all(np.isfinite(w) & (w >= 0.0) & (w <= 1.0)):
-        raise ValueError("row weights: m entries, each finite and in [0, 1]")
-    return w
-
-
-def _wcentre(w, v):
-    """v - (sum w v / sum w) at every row (unweighted); v itself when sum w = 0."""
-    nw = float(w.sum())
-    return v - (float(w @ v) / nw if nw > 0 else 0.0)
-
-
-def weighted_panel_iterate(A, b, w, mu, iters, diag=None, x0=None, intercept=False, positive=False, p=None):
-    """``iters`` updates (one feature block) of the panel's iteration on the weighted problem of one right-hand
-    side, in fp64.  The carried residual is R^ = w o (A x - b) (w o (e - ebar_w) with ``intercept``, ebar_w the
-    weighted mean); G = A^T R^; the prox of ``penalty_panel_iterate`` with ``diag`` (default the FULL column norms,
-    ``centred_diag(A)`` with ``intercept``: d_j >= sum_i w_i a_ij^2 because w <= 1); s = A D and s^ = w o s; the exact
-    line search of the weighted objective along D, gamma = clip(-(R^ . s + mu (sum p |x + D| - sum p |x|)) /
-    (s . s^ - c sum s^), 0, 1) with c = sum s^ / sum w under ``intercept`` and 0 otherwise (gamma = 0 when the
-    curvature is <= 0); x += gamma D and R^ += gamma (s^ - c w).  ``w``: (m,), every entry finite and in [0, 1]
-    (ValueError otherwise).  ``p`` None: all ones.  With ``positive`` ``x0`` is projected to max(x0, 0).  Returns
-    dict(x, r[, intercept]) with r = R^ and intercept = -sum w (A x - b) / sum w."""
-    A = np.asarray(A, dtype=np.float64)
-    m, n = A.shape
-    b = np.asarray(b, dtype=np.float64).reshape(-1)
-    w = _row_weights(w, m)
-    nw = float(w.sum())
-    mu = float(mu)
-    pw = np.ones(n) if p is None else _penalty(p, n)
-    if diag is None:
-        dg = centred_diag(A) if intercept else np.square(A).sum(axis=0)
-    else:
-        dg = np.asarray(diag, dtype=np.float64).reshape(-1)
-    with np.errstate(divide="ignore"):
-        rec = np.where(dg > 0, 1.0 / np.where(dg > 0, dg, 1.0), 0.0)
-    x = np.zeros(n) if x0 is None else np.array(x0, dtype=np.float64).reshape(-1)
-    if positive:
-        x = np.maximum(x, 0.0)
-    e = A @ x - b
-    R = w * (_wcentre(w, e) if intercept else e)
-    for _ in range(int(iters)):
-        g = A.T @ R
-        rx = dg * x - g
-        Bx = rec * (np.sign(rx) * np.maximum(np.abs(rx) - mu * pw, 0))
-        if positive:
-            Bx = np.maximum(Bx, 0.0)
-        D = Bx - x
-        s = A @ D
-        sh = w * s
-        sm = float(sh.sum())
-        c = (sm / nw if nw > 0 else 0.0) if intercept else 0.0
-        l1d = np.where(x * Bx > 0, np.sign(x) * D, np.abs(Bx) - np.abs(x))   # as in penalty_panel_iterate
-        r1 = R @ s + mu * float(pw @ l1d)
         r2 = s @ sh - c * sm
         gamma = 0.0 if r2 <= 0 else float(np.clip(-r1 / r2, 0, 1))
-        x = x + gamma * D
+        x[mb] = x[mb] + gamma * D
         R = R + gamma * (sh - c * w)
-    out = dict(x=x, r=R)
+    out = dict(x=x.reshape(-1), r=R)
     if intercept:
-        e = A @ x - b
-        out["intercept"] = -(float(w @ e) / nw) if nw > 0 else 0.0
+        out["intercept"] = -_wmean(w, A @ out["x"] - b) if nw > 0 else 0.0
     return out
 
 
-def weighted_duality_gap(A, b, w, x, mu, diag=None, intercept=False, positive=False, p=None, hold=None):
-    """The certificate of the weighted problem at x (x >= 0 with ``positive``): e = A x - b (minus its weighted mean
-    with ``intercept``), r = w o e, g = A^T r; primal = 1/2 sum w e^2 + mu sum p_j |x_j|, and with gnorm_inf =
-    max_j |g_j| / p_j (max_j (-g_j)+ / p_j with ``positive``) and scale = min(1, mu / gnorm_inf) (1 when that is 0),
-    dual = -1/2 scale^2 sum w e^2 - scale sum w e b, gap = primal - dual.  The dual point is theta_i = scale
-    sqrt(w_i) e_i of the problem on (diag(sqrt w) A, sqrt(w) o b); it is never formed.  The gap-safe score is
-    scale |g_j| + sqrt(d_j) sqrt(2 max(gap, 0)) (-g_j with ``positive``), keep_j = not (score_j < mu p_j), with ``diag``
-    (default the FULL column norms, ``centred_diag(A)`` with ``intercept``, safe because w <= 1).  holdout_sse =
-    sum_i h_i (a_i . x + intercept - b_i)^2 with ``hold`` = h >= 0 (default 1 where w = 0, else 0); intercept =
-    -sum w (A x - b) / sum w with ``intercept``, else 0."""
+def _panel_gap(A, b, w, x, mu, p, diag, intercept, positive, hold):
+    """The certificate at x (x >= 0 with ``positive``), arguments as ``_panel_iterate``: e = A x - b (minus its
+    weighted mean c with ``intercept``, so that r sums to zero: the intercept's dual constraint), r = w o e,
+    g = A^T r; primal = 1/2 sum w e^2 + mu sum p_j |x_j|.  The dual constraint is |a_j . theta| <= mu p_j
+    (-a_j . theta <= mu p_j with ``positive``), so gnorm_inf = max_j |g_j| / p_j (max_j (-g_j)+ / p_j; NaN propagates;
+    at x = 0 it is mu_max) and scale = min(1, mu / gnorm_inf) (1 when that is 0) makes scale r dual feasible:
+    dual = -1/2 scale^2 sum w e^2 - scale sum w e b, gap = primal - dual >= P(x) - P*.  The dual point is theta_i =
+    scale sqrt(w_i) e_i of the problem on (diag(sqrt w) A, sqrt(w) o b); it is never formed.  The gap-safe score is
+    scale |g_j| + sqrt(d_j) sqrt(2 max(gap, 0)) (-g_j for |g_j| with ``positive``) and keep_j = not (score_j < mu p_j):
+    a column that is not kept is 0 at every optimum, and a NaN keeps everything.  holdout_sse = sum_i h_i (a_i . x +
+    intercept - b_i)^2 with ``hold`` = h >= 0 (default 1 where w = 0, else 0); intercept = -c with ``intercept``, else
+    0.  Returns dict(primal, dual, gap, scale, gnorm_inf, holdout_sse, intercept, score, keep, g, r)."""
     A = np.asarray(A, dtype=np.float64)
-    m, n = A.shape
     b = np.asarray(b, dtype=np.float64).reshape(-1)
     x = np.asarray(x, dtype=np.float64).reshape(-1)
-    w = _row_weights(w, m)
     nw = float(w.sum())
     mu = float(mu)
-    pw = np.ones(n) if p is None else _penalty(p, n)
+    pw = np.ones(A.shape[1]) if p is None else p
     h = (w == 0.0).astype(np.float64) if hold is None else np.asarray(hold, dtype=np.float64).reshape(-1)
     e = A @ x - b
-    c = (float(w @ e) / nw if nw > 0 else 0.0) if intercept else 0.0
+    c = _wmean(w, e) if intercept else 0.0
     ec = e - c
     r = w * ec
     g = A.T @ r
@@ -596,13 +339,64 @@ def weighted_duality_gap(A, b, w, x, mu, diag=None, intercept=False, positive=Fa
     scale = min(1.0, mu / gn) if gn > 0.0 else 1.0
     dual = -0.5 * scale * scale * wee - scale * float(r @ b)
     gap = primal - dual
-    if diag is None:
-        dg = centred_diag(A) if intercept else np.square(A).sum(axis=0)
-    else:
-        dg = np.asarray(diag, dtype=np.float64).reshape(-1)
+    dg = _diag_in_effect(A, diag, intercept)
     score = scale * (-g if positive else np.abs(g)) + np.sqrt(dg) * np.sqrt(2.0 * np.maximum(gap, 0.0))
     return dict(primal=primal, dual=dual, gap=gap, scale=scale, gnorm_inf=gn, holdout_sse=float(h @ (ec * ec)),
                 intercept=-c if (intercept and nw > 0) else 0.0, score=score, keep=~(score < mu * pw), g=g, r=r)
+
+
+# Intercept, 0/1 rows, one feature block.
+def intercept_panel_iterate(A, b, w, mu, iters, diag=None, x0=None):
+    """``_panel_iterate`` with the intercept on the masked problem; ``diag``: default ``centred_diag(A)``.  Returns
+    dict(x, r, intercept)."""
+    return _panel_iterate(A, b, _rows01(w, A), mu, None, 1, iters, diag, x0, True, False)
+
+
+def intercept_duality_gap(A, b, w, x, mu, diag=None):
+    """``_panel_gap`` with the intercept on the masked problem; ``diag``: default ``centred_diag(A)``."""
+    return _panel_gap(A, b, _rows01(w, A), x, mu, None, diag, True, False, None)
+
+
+# Non-negative lasso (DESIGN.md section 14): x >= 0, 0/1 rows (``w`` None: all rows), with or without the intercept.
+def positive_panel_iterate(A, b, w, mu, Block, iters, diag=None, x0=None, intercept=False):
+    """``_panel_iterate`` with the sign constraint: the one-sided prox, ``x0`` projected to max(x0, 0), x >= 0 at
+    every iteration."""
+    return _panel_iterate(A, b, _rows01(w, A), mu, None, Block, iters, diag, x0, intercept, True)
+
+
+def positive_duality_gap(A, b, w, x, mu, diag=None, intercept=False):
+    """``_panel_gap`` with the sign constraint at a feasible x: the one-sided gnorm_inf and score."""
+    return _panel_gap(A, b, _rows01(w, A), x, mu, None, diag, intercept, True, None)
+
+
+# Penalty factors (DESIGN.md section 15): per-column l1 weights ``p``, (n,), every entry finite and > 0 (ValueError
+# otherwise), used as given (no renormalisation to sum p = n); 0/1 rows (``w`` None: all rows).
+def penalty_panel_iterate(A, b, w, mu, p, Block, iters, diag=None, x0=None, intercept=False, positive=False):
+    """``_panel_iterate`` with the factors ``p``."""
+    return _panel_iterate(A, b, _rows01(w, A), mu, _penalty(p, np.shape(A)[1]), Block, iters, diag, x0, intercept,
+                          positive)
+
+
+def penalty_duality_gap(A, b, w, x, mu, p, diag=None, intercept=False, positive=False):
+    """``_panel_gap`` with the factors ``p``."""
+    return _panel_gap(A, b, _rows01(w, A), x, mu, _penalty(p, np.shape(A)[1]), diag, intercept, positive, None)
+
+
+# Observation weights (DESIGN.md section 16): ``w`` (m,), every entry finite and in [0, 1] (ValueError otherwise);
+# ``p`` None: all ones.  One feature block, as the device has it.
+def weighted_panel_iterate(A, b, w, mu, iters, diag=None, x0=None, intercept=False, positive=False, p=None):
+    """``_panel_iterate`` with general row weights."""
+    m, n = np.shape(A)
+    return _panel_iterate(A, b, _row_weights(w, m), mu, None if p is None else _penalty(p, n), 1, iters, diag, x0,
+                          intercept, positive)
+
+
+def weighted_duality_gap(A, b, w, x, mu, diag=None, intercept=False, positive=False, p=None, hold=None):
+    """``_panel_gap`` with general row weights; ``hold``: the held-out score's weights h >= 0 (default 1 where
+    w = 0, else 0)."""
+    m, n = np.shape(A)
+    return _panel_gap(A, b, _row_weights(w, m), x, mu, None if p is None else _penalty(p, n), diag, intercept, positive,
+                      hold)
 
 
 # ---------------------------------------------------------------------------

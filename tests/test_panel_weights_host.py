@@ -7,7 +7,7 @@
     parity bound; with ``positive`` / ``p`` against ``positive_panel_iterate`` / ``penalty_panel_iterate`` there.  With
     the intercept the scaled problem's unpenalised column is sqrt(omega), not a constant, so the plain restatement runs
     on the scaled data projected off u = sqrt(omega) / |sqrt(omega)| (profiling that column out).  With 0/1 weights it
-    is ``masked_panel_iterate`` / ``intercept_panel_iterate`` to the same bound.
+    is ``masked_panel_iterate`` to the same bound, on the row-deleted and explicitly centred problem with the intercept.
 (3) ``weighted_duality_gap`` against ``masked_duality_gap`` of the scaled (projected) problem: scalars to 1e-12 relative;
     dual <= the primal of a long fp64 run (weak duality); that run's support lies inside keep.
 (4) ``panel_weight_reference.check_step_weighted`` separates right from wrong.  The "device" is ``WModel``, a numpy model
@@ -107,14 +107,27 @@ def test_restatement_is_the_scaled_problem(intercept, positive, use_p):
 
 @pytest.mark.parametrize("intercept", [False, True])
 def test_zero_one_weights_are_the_masked_restatement(intercept):
+    """With the intercept ``intercept_panel_iterate`` is the same code as ``weighted_panel_iterate``, so the reference
+    is ``masked_panel_iterate`` on the row-deleted, explicitly centred problem (as
+    panel_intercept_instance.row_deleted_reference builds it), the centred data's own column norms handed to both."""
     A, b, om, _ = small(1)
     w = (om > 0.5).astype(np.float64)
-    dg = C.centred_diag(A) if intercept else np.square(A).sum(axis=0)
+    idx = w != 0
     mu = 0.2 * float(np.max(np.abs(A.T @ (w * b))))
+    if intercept:
+        Ai, bi = A[idx] - A[idx].mean(axis=0), b[idx] - b[idx].mean()
+        dg = np.square(Ai).sum(axis=0)
+    else:
+        dg = np.square(A).sum(axis=0)
     for iters in (1, 2, 3, 5, 8, 12):
         got = C.weighted_panel_iterate(A, b, w, mu, iters, diag=dg, intercept=intercept)
-        ref = C.intercept_panel_iterate(A, b, w, mu, iters, diag=dg) if intercept else \
-            C.masked_panel_iterate(A, b, w, mu, 1, iters, diag=dg)
+        if intercept:
+            sub = C.masked_panel_iterate(Ai, bi, np.ones(int(idx.sum())), mu, 1, iters, diag=dg)
+            r = np.zeros(A.shape[0])                 # the held-out rows of the carried residual are 0
+            r[idx] = sub["r"]
+            ref = dict(x=sub["x"], r=r, intercept=float(b[idx].mean() - A[idx].mean(axis=0) @ sub["x"]))
+        else:
+            ref = C.masked_panel_iterate(A, b, w, mu, 1, iters, diag=dg)
         np.testing.assert_allclose(got["x"], ref["x"], rtol=0, atol=REL * np.abs(ref["x"]).max())
         np.testing.assert_allclose(got["r"], ref["r"], rtol=0, atol=REL * np.abs(ref["r"]).max())
         if intercept:
