@@ -26,7 +26,9 @@ restatement of the panel's row-masked problems (K-fold cross-validation, DESIGN.
 (per-column l1 weights) and observation weights (DESIGN.md sections 13-16).  Those pairs and
 ``masked_duality_gap`` are thin wrappers of ONE statement of the iteration and ONE of the certificate,
 ``_panel_iterate`` and ``_panel_gap``; ``masked_panel_iterate`` alone stands beside them,
-pinned bitwise to the C oracle.
+pinned bitwise to the C oracle.  ``logistic_model``, ``logistic_gap`` and ``logistic_panel_solve`` (with
+``logistic_intercept``, ``logistic_dual`` and ``logistic_null_deviance``) restate the logistic lasso's outer step, its
+certificate and its IRLS loop, ``_panel_iterate`` being the inner solve.
 """
 import numpy as np
 
@@ -416,3 +418,220 @@ def compaction_columns(keep_union, q):
     n_new = max(q, -(-kept.size // q) * q)
     pads = np.flatnonzero(~keep)[:n_new - kept.size]
     return np.sort(np.concatenate([kept, pads])).astype(np.int64)
+
+
+# ---------------------------------------------------------------------------
+# Logistic lasso by IRLS on the weighted panel: the host restatement of bpgl_panel_glm_model,
+# bpgl_panel_glm_dual and the outer loop of ``panel.logistic_path``.
+#   min over x, beta0 of sum_i om_i l(eta_i; y_i) + mu sum_j p_j |x_j|,  eta = A x + beta0,  l = log(1 + e^eta) - y eta
+# with labels y in [0, 1], prior weights om in [0, 1]; x >= 0 with ``positive``; beta0 = 0 without the intercept.
+# ---------------------------------------------------------------------------
+GLM_FLOOR = 1e-5          # glmnet's floor of p (1 - p)
+GLM_PHI_TOL = 1e-14       # the intercept's Newton iteration stops at |phi| <= this x sum om
+GLM_NEWTON_MAX = 40
+
+
+def _wave_fold(v):
+    """(..., 64) -> (...): the device's wave_sum, lanes l and l ^ o added for o = 32, 16, ..., 1."""
+    for o in (32, 16, 8, 4, 2, 1):
+        v = v[..., :o] + v[..., o:2 * o]
+    return v[..., 0]
+
+
+def _block_sum(v):
+    """The device's one-block sum of a vector: 256 threads, thread t adding entries t, t + 256, ... in index order,
+    the lanes of each wave by ``_wave_fold``, the 4 waves in order."""
+    v = np.asarray(v, dtype=np.float64).reshape(-1)
+    rows = -(-v.size // 256)
+    v = np.concatenate([v, np.zeros(rows * 256 - v.size)]).reshape(rows, 256)
+    t = np.zeros(256)
+    for r in v:
+        t = t + r
+    w = _wave_fold(t.reshape(4, 64))
+    return float(((w[0] + w[1]) + w[2]) + w[3])
+
+
+def _blocks_sum(v):
+    """The device's sum of one value per (rhs, row) thread: per 256-row block the lanes and the 4 waves in order, then
+    the blocks in block order."""
+    v = np.asarray(v, dtype=np.float64).reshape(-1, 4, 64)
+    w = _wave_fold(v)
+    tot = 0.0
+    for b in ((w[:, 0] + w[:, 1]) + w[:, 2]) + w[:, 3]:
+        tot += float(b)
+    return tot
+
+
+def _sigma(eta):
+    t = np.exp(-np.abs(eta))
+    return np.where(eta >= 0, 1.0 / (1.0 + t), t / (1.0 + t))
+
+
+def _logloss(eta, y):
+    return np.maximum(eta, 0.0) + np.log1p(np.exp(-np.abs(eta))) - y * eta
+
+
+def _labels(y, m):
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    if y.size != m or not np.all(np.isfinite(y) & (y >= 0.0) & (y <= 1.0)):
+        raise ValueError("labels: m entries, each in [0, 1]")
+    return y
+
+
+def _neg_entropy(t):
+    """Nh(t) = t log t + (1 - t) log(1 - t) with 0 log 0 = 0 (a t rounded outside [0, 1] counts as the end point)."""
+    u = 1.0 - t
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(t > 0, t * np.log(np.where(t > 0, t, 1.0)), 0.0) + \
+            np.where(u > 0, u * np.log(np.where(u > 0, u, 1.0)), 0.0)
+
+
+def logistic_null_deviance(y, omega, intercept=True):
+    """sum om l at x = 0 and its own beta0: -sum om Nh(ybar) with the intercept (ybar the weighted mean label),
+    sum om log 2 without.  The scale of the logistic stopping rule, as 1/2 ||b||^2 is of the lasso's."""
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    om = np.asarray(omega, dtype=np.float64).reshape(-1)
+    sw = float(om.sum())
+    if not intercept:
+        return sw * float(np.log(2.0))
+    return -sw * float(_neg_entropy(np.float64(float(om @ y) / sw)))
+
+
+def logistic_intercept(ax, y, omega, beta0=0.0):
+    """The root of phi(beta) = sum om (sigma(ax + beta) - y) by the device's safeguarded Newton iteration: the
+    bracket [logit(ybar) - max ax, logit(ybar) - min ax] over the rows with a weight, the start ``beta0`` (the
+    midpoint when outside), a step that leaves the bracket replaced by the midpoint, at most GLM_NEWTON_MAX steps, stop
+    at |phi| <= GLM_PHI_TOL sum om; fixed-order sums.  Returns (beta, |phi|, steps, flag); flag 1 (and ``beta0`` back)
+    when sum om y is 0 or sum om: no finite root."""
+    sw, sy = _block_sum(omega), _block_sum(omega * y)
+
+    def ev(beta):
+        p = _sigma(ax + beta)
+        return _block_sum(omega * (p - y)), _block_sum(omega * (p * (1.0 - p)))
+    beta = float(beta0)
+    if not (sy > 0.0 and sy < sw):
+        return beta, abs(ev(beta)[0]), 0, 1
+    lg = float(np.log(sy / (sw - sy)))
+    live = omega > 0
+    lo, hi = lg - float(ax[live].max()), lg + float((-ax[live]).max())
+    if not (lo <= beta <= hi):
+        beta = 0.5 * (lo + hi)
+    steps = 0
+    while True:
+        f, d = ev(beta)
+        if abs(f) <= GLM_PHI_TOL * sw or steps == GLM_NEWTON_MAX:
+            break
+        if f > 0.0:
+            hi = beta
+        else:
+            lo = beta
+        nb = beta - f / d if d > 0.0 else lo
+        if not (lo < nb < hi):
+            nb = 0.5 * (lo + hi)
+        beta = nb
+        steps += 1
+    return beta, abs(f), steps, 0
+
+
+def logistic_model(A, y, omega, x, beta0=0.0, intercept=True, curv=0, hold=None, p=None, solve=True):
+    """One outer step at x, the restatement of bpgl_panel_glm_model for one right-hand side: ax = A x; beta0 the root of
+    phi with ``intercept`` (``solve=False``: ``beta0`` as given; without ``intercept`` 0); eta = ax + beta0,
+    p = sigma(eta), v = max(p (1 - p), GLM_FLOOR) (1/4 with ``curv``: Boehning's bound), w = 4 om v, z = eta + (y - p) / v;
+    loss = sum om l, hold_loss = sum h l, hold_miss = sum h [(p > 1/2) != (y > 1/2)] (``hold`` = h, None: zeros),
+    sum_omega, l1 = sum pen_j |x_j| (``p`` = pen, None: ones), phi = |phi(beta0)|, steps, flag.  The block sums follow the
+    device's order."""
+    A = np.asarray(A, dtype=np.float64)
+    m, n = A.shape
+    y = _labels(y, m)
+    om = _row_weights(omega, m)
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    pw = np.ones(n) if p is None else _penalty(p, n)
+    h = np.zeros(m) if hold is None else np.asarray(hold, dtype=np.float64).reshape(-1)
+    ax = A @ x
+    if intercept and solve:
+        b0, phi, steps, flag = logistic_intercept(ax, y, om, beta0)
+    else:
+        b0 = float(beta0) if intercept else 0.0
+        phi, steps, flag = abs(_block_sum(om * (_sigma(ax + b0) - y))), 0, 0
+    eta = ax + b0
+    pr = _sigma(eta)
+    v = np.full(m, 0.25) if curv else np.maximum(pr * (1.0 - pr), GLM_FLOOR)
+    ls = _logloss(eta, y)
+    miss = ((pr > 0.5) != (y > 0.5)).astype(np.float64)
+    tot = _blocks_sum if m % 256 == 0 else _block_sum
+    return dict(ax=ax, beta0=b0, eta=eta, p=pr, v=v, w=(4.0 * om) * v, z=eta + (y - pr) / v,
+                loss=tot(om * ls), hold_loss=tot(h * ls), hold_miss=tot(h * miss), sum_omega=tot(om),
+                l1=_block_sum(pw * np.abs(x)), phi=phi, steps=steps, flag=flag)
+
+
+def logistic_dual(y, omega, p, scale):
+    """D = -sum om Nh(s p + (1 - s) y): the dual value at theta = s om o (p - y) (bpgl_panel_glm_dual)."""
+    s = float(scale)
+    return -_block_sum(omega * _neg_entropy(s * p + (1.0 - s) * y))
+
+
+def logistic_gap(A, y, omega, x, mu, beta0=0.0, intercept=True, positive=False, p=None, model=None):
+    """The logistic certificate at x: with the model's p (``model``: a ``logistic_model`` of the same arguments, else
+    computed here, beta0 re-solved), g = A^T (om o (p - y)) the loss's gradient, gnorm_inf = max_j |g_j| / pen_j
+    (max_j (-g_j)+ / pen_j with ``positive``; at x = 0 it is mu_max), scale = min(1, mu / gnorm_inf) (1 when that is 0):
+    theta = scale om o (p - y) satisfies |a_j . theta| <= mu pen_j and, beta0 being the root of phi, sum theta = 0.
+    primal = sum om l + mu sum pen |x|, dual = ``logistic_dual``, gap = primal - dual >= P(x, beta0) - P*.
+    Returns dict(primal, dual, gap, scale, gnorm_inf, g, beta0)."""
+    A = np.asarray(A, dtype=np.float64)
+    mod = logistic_model(A, y, omega, x, beta0, intercept, 0, None, p) if model is None else model
+    om = _row_weights(omega, A.shape[0])
+    yv = _labels(y, A.shape[0])
+    pw = np.ones(A.shape[1]) if p is None else _penalty(p, A.shape[1])
+    mu = float(mu)
+    g = A.T @ (om * (mod["p"] - yv))
+    ga = np.where(g > 0, 0.0, -g) if positive else np.abs(g)
+    gn = float(np.max(ga / pw))
+    scale = min(1.0, mu / gn) if gn > 0.0 else 1.0
+    primal = mod["loss"] + mu * mod["l1"]
+    dual = logistic_dual(yv, om, mod["p"], scale)
+    return dict(primal=primal, dual=dual, gap=primal - dual, scale=scale, gnorm_inf=gn, g=g, beta0=mod["beta0"])
+
+
+def logistic_panel_solve(A, y, omega, mu, outer_max=100, inner_iters=16, tol=1e-8, intercept=True, positive=False,
+                         p=None, curv=0, x0=None, diag=None, round_x=False):
+    """The IRLS outer loop on one right-hand side, ``_panel_iterate`` as the inner solve.  Per outer step, at the
+    current x: ``logistic_model`` (beta0 re-solved from the last one); P = loss + mu l1; a P above the previous one
+    switches to ``curv`` = 1 from then on (the model is formed again with it); the certificate ``logistic_gap``; stop
+    when gap <= ``tol`` x the null deviance or after ``outer_max`` steps; else ``inner_iters`` iterations on
+    1/2 sum w (a . x + beta0 - z)^2 + 4 mu sum pen |x| from x (x >= 0 with ``positive``), whose weighted-mean intercept is
+    the next Newton start.  ``round_x``: x is rounded to fp32 after every inner solve, as the device stores it.
+    Returns dict(x, intercept, primal, dual, gap, scale, null_deviance, reached, outer_iters, curvature, history (P at
+    every outer step))."""
+    A = np.asarray(A, dtype=np.float64)
+    m, n = A.shape
+    yv, om = _labels(y, m), _row_weights(omega, m)
+    pen = None if p is None else _penalty(p, n)
+    mu = float(mu)
+    null = logistic_null_deviance(yv, om, intercept)
+    x = np.zeros(n) if x0 is None else np.array(x0, dtype=np.float64).reshape(-1)
+    if positive:
+        x = np.maximum(x, 0.0)
+    if round_x:
+        x = x.astype(np.float32).astype(np.float64)
+    b0, curv, hist, outer = 0.0, int(bool(curv)), [], 0
+    while True:
+        mod = logistic_model(A, yv, om, x, b0, intercept, curv, None, pen)
+        P = mod["loss"] + mu * mod["l1"]
+        if hist and not curv and P > hist[-1]:
+            curv = 1
+            mod = logistic_model(A, yv, om, x, b0, intercept, curv, None, pen)
+        b0 = mod["beta0"]
+        cert = logistic_gap(A, yv, om, x, mu, b0, intercept, positive, pen, model=mod)
+        hist.append(P)
+        if cert["gap"] <= tol * null or outer >= int(outer_max):
+            break
+        inner = _panel_iterate(A, mod["z"], mod["w"], 4.0 * mu, pen, 1, inner_iters, diag, x, intercept, positive)
+        x = inner["x"]
+        if round_x:
+            x = x.astype(np.float32).astype(np.float64)
+        if intercept:
+            b0 = inner["intercept"]
+        outer += 1
+    return dict(x=x, intercept=b0, primal=cert["primal"], dual=cert["dual"], gap=cert["gap"], scale=cert["scale"],
+                null_deviance=null, reached=bool(cert["gap"] <= tol * null), outer_iters=outer, curvature=curv,
+                history=np.array(hist))

@@ -665,7 +665,7 @@ const Knob kKnobs[] = {
 extern "C" {
 
 const char* bpgl_last_error(void) { return bpgl_host::g_err.c_str(); }
-int bpgl_version(void) { return 310; }
+int bpgl_version(void) { return 311; }
 
 int bpgl_stream_create(int device, const uint32_t* cu_mask, int32_t mask_words, void** out) {
     if (!out) return fail(BPGL_E_ARG, "out is null");

@@ -17,6 +17,7 @@
 #include "bpgl_panel_pos.h"
 #include "bpgl_panel_pen.h"
 #include "bpgl_panel_wt.h"
+#include "bpgl_panel_glm.h"
 
 using namespace bpgl;
 using namespace bpgl_host;
@@ -29,7 +30,8 @@ constexpr int kPanelKinds = 5;   // pass1, pass2, reduce, step, update
 // byte offsets of the scratch regions (panel_layout), in the order they are laid out
 struct PanelLayout {
     int64_t st, Rh, Rl, Dh, Dl, X, Ax, B, R, diag, rec, Sslab, S, norms, lsp, mu, gamma, err_rhs, cnt, ready, lsdone, Gc,
-        Sh, Ec, At, A1t, gpart, gparts, gcounts, gres, W, Bh, ghold, lss, cshift, nw, bmean, gipart, gicp, pen, Wt, Hd, gE, total;
+        Sh, Ec, At, A1t, gpart, gparts, gcounts, gres, W, Bh, ghold, lss, cshift, nw, bmean, gipart, gicp, pen, Wt, Hd, gE,
+        glmAX, glmpart, glmres, glmsd, total;
 };
 
 struct bpgl_panel {
@@ -66,6 +68,7 @@ struct bpgl_panel {
                                   // and `masked` is then false: the weights stand where the mask would)
     bool icpt_valid = false;      // a bpgl_panel_gap has run since the last reset: icpt_host is its beta0
     std::vector<double> icpt_host;
+    bool have_x = false;          // a reset has run since bind: X is an iterate (bpgl_panel_glm_model needs one)
     char* scratch = nullptr;      // the caller's scratch and its layout (bpgl_panel_bind)
     PanelLayout L{};
     template <typename T>
@@ -176,6 +179,12 @@ PanelLayout panel_layout(const bpgl_panel* c) {
     L.Wt = k.take(8 * km);
     L.Hd = k.take(8 * km + 256);
     L.gE = k.take(8 * km);
+    // the logistic model (bpgl_panel_glm_model / _dual): A x, the model kernel's block partials, the scalars, and the
+    // dual call's scale and result.  After everything else once more.
+    L.glmAX = k.take(8 * km);
+    L.glmpart = k.take(8 * (int64_t)bpgl_glm::kGlmPart * (km / kThreads));
+    L.glmres = k.take(8 * (int64_t)bpgl_glm::kGlmRes * c->k);
+    L.glmsd = k.take(8 * 2 * (int64_t)c->k);
     L.total = k.off;
     return L;
 }
@@ -436,6 +445,23 @@ int panel_ready(const bpgl_panel* c) {
     if (!c->bound) return fail(BPGL_E_STATE, "bpgl_panel_bind has not been called");
     return 0;
 }
+// the logistic model's view of the context (bpgl_panel_glm.h); the caller's pointers are filled in by the two calls
+bpgl_glm::GlmArgs glm_args(const bpgl_panel* c) {
+    bpgl_glm::GlmArgs g{};
+    g.m = c->m;
+    g.n = c->n;
+    g.k = c->k;
+    g.icpt = c->icpt ? 1 : 0;
+    g.X = c->p.X;
+    g.pen = c->penalty ? c->at<double>(c->L.pen) : nullptr;
+    g.part = c->at<double>(c->L.gpart);
+    g.AX = c->at<double>(c->L.glmAX);
+    g.bpart = c->at<double>(c->L.glmpart);
+    g.res = c->at<double>(c->L.glmres);
+    g.scale = c->at<double>(c->L.glmsd);
+    g.dual = c->at<double>(c->L.glmsd) + c->k;
+    return g;
+}
 }  // namespace
 
 extern "C" {
@@ -564,6 +590,7 @@ int bpgl_panel_bind(bpgl_panel* c, const void* A, int64_t lda, void* scratch, in
     c->masked = c->user_mask = c->icpt = c->icpt_valid = c->positive = c->penalty = c->weighted = false;   // p.W, p.Wt are null again
     panel_fuse_check(c);
     c->bound = true;
+    c->have_x = false;
     c->have_diag = false;
     c->solver = false;
     drop_graphs(c);
@@ -694,6 +721,7 @@ int bpgl_panel_reset_x0(bpgl_panel* c, const double* B, const double* mu, const 
         if (rc) return rc;
     }
     c->solver = true;
+    c->have_x = true;
     c->tm.iters = 0;
     return 0;
 }
@@ -829,6 +857,7 @@ int bpgl_panel_stat(const bpgl_panel* c, const char* key, int64_t* value) {
     else if (!strcmp(key, "fuse_cus")) *value = c->fuse_cus;   // CUs the fused-update check counted
     else if (!strcmp(key, "gap_prod1_ns")) *value = c->gap_ns[0];   // the last bpgl_panel_gap: R_fresh = A X - B
     else if (!strcmp(key, "gap_prod2_ns")) *value = c->gap_ns[1];   // ... and G = A^T R_fresh
+    else if (!strcmp(key, "glm_ax_offset")) *value = c->L.glmAX;    // bpgl_panel_glm_model's A x [nrhs][m] fp64: its byte offset in the scratch
     else return fail(BPGL_E_ARG, "unknown panel stat '%s'", key);
     return 0;
 }
@@ -1011,6 +1040,70 @@ int bpgl_panel_gap(bpgl_panel* c, double* G_all, double* R_fresh, uint8_t* keep,
     }
     if (!keep)
         for (int k = 0; k < c->k; ++k) out[(int64_t)k * kPgRes + 5] = (double)c->n;
+    return 0;
+}
+
+int bpgl_panel_glm_model(bpgl_panel* c, int family, const double* Y, const double* Om, const double* Hd,
+                         const int32_t* curv, double* beta0, double* W, double* Z, double* P, double* out) {
+    int rc;
+    if ((rc = panel_ready(c))) return rc;
+    if (family != BPGL_GLM_BINOMIAL) return fail(BPGL_E_ARG, "family must be BPGL_GLM_BINOMIAL (got %d)", family);
+    if (!Y || !Om || !beta0 || !W || !Z || !P || !out)
+        return fail(BPGL_E_ARG, "Y, Om, beta0, W, Z, P and out must be non-null");
+    if (((uintptr_t)Y | (uintptr_t)Om | (uintptr_t)Hd | (uintptr_t)beta0 | (uintptr_t)W | (uintptr_t)Z | (uintptr_t)P) % 8 ||
+        ((uintptr_t)curv) % 4)
+        return fail(BPGL_E_ARG, "Y, Om, Hd, beta0, W, Z and P must be 8-byte aligned, curv 4-byte aligned");
+    if (c->nblock != 1) return fail(BPGL_E_STATE, "the logistic model needs one feature block (nblock is %d)", c->nblock);
+    if (!c->have_x) return fail(BPGL_E_STATE, "bpgl_panel_reset has not been called since bpgl_panel_bind");
+    if ((rc = bpgl_panel_status(c, nullptr, nullptr))) return rc;   // waits; reports a failed exchange
+    // A x through the certificate's product 1, its chunking and its launch; the fold subtracts nothing
+    PanelGapArgs a = pgap_args(c);
+    a.spl = pgap_split(c->m / kPgTile, c->n / kPgK);
+    a.chunk = c->n / kPgK / a.spl;
+    const dim3 blk(kThreads);
+    const auto prod = dispatch_nt(c->k, [](auto nt) { return &k_pgap_prod<decltype(nt)::value, 1>; });
+    hipLaunchKernelGGL(prod, dim3((unsigned)(c->m / kPgTile * a.spl)), blk, 0, c->stream, a);
+    LAUNCH_CHECK("k_pgap_prod");
+    bpgl_glm::GlmArgs g = glm_args(c);
+    g.spl = a.spl;
+    g.Y = Y;
+    g.Om = Om;
+    g.Hd = Hd;
+    g.curv = curv;
+    g.beta0 = beta0;
+    g.W = W;
+    g.Z = Z;
+    g.P = P;
+    const dim3 rows((unsigned)((int64_t)c->k * c->m / kThreads)), rhs((unsigned)c->k);
+    hipLaunchKernelGGL(bpgl_glm::fold(), rows, blk, 0, c->stream, g);
+    LAUNCH_CHECK("k_glm_fold");
+    hipLaunchKernelGGL(bpgl_glm::newton(), rhs, blk, 0, c->stream, g);
+    LAUNCH_CHECK("k_glm_newton");
+    hipLaunchKernelGGL(bpgl_glm::model(), rows, blk, 0, c->stream, g);
+    LAUNCH_CHECK("k_glm_model");
+    hipLaunchKernelGGL(bpgl_glm::l1_final(), rhs, blk, 0, c->stream, g);
+    LAUNCH_CHECK("k_glm_l1_final");
+    HIP_TRY(hipMemcpyAsync(out, g.res, sizeof(double) * bpgl_glm::kGlmRes * c->k, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int bpgl_panel_glm_dual(bpgl_panel* c, const double* P, const double* Y, const double* Om, const double* scale,
+                        double* out) {
+    int rc;
+    if ((rc = panel_ready(c))) return rc;
+    if (!P || !Y || !Om || !scale || !out) return fail(BPGL_E_ARG, "P, Y, Om, scale and out must be non-null");
+    if (((uintptr_t)P | (uintptr_t)Y | (uintptr_t)Om) % 8) return fail(BPGL_E_ARG, "P, Y and Om must be 8-byte aligned");
+    HIP_TRY(hipSetDevice(c->device));
+    bpgl_glm::GlmArgs g = glm_args(c);
+    g.P = const_cast<double*>(P);
+    g.Y = Y;
+    g.Om = Om;
+    HIP_TRY(hipMemcpyAsync(const_cast<double*>(g.scale), scale, 8 * (int64_t)c->k, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(bpgl_glm::dual_sum(), dim3((unsigned)c->k), dim3(kThreads), 0, c->stream, g);
+    LAUNCH_CHECK("k_glm_dual");
+    HIP_TRY(hipMemcpyAsync(out, g.dual, 8 * (int64_t)c->k, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
 

@@ -48,6 +48,10 @@ and ``lasso_path`` / ``lasso_cv`` take ``penalty_factors`` (DESIGN.md section 15
 scikit-learn's ``sample_weight``) and scoring weights for the held-out score, on the A that is bound -- no row-rescaled
 copy -- and ``lasso_path`` / ``lasso_cv`` take ``sample_weight`` (any scale, used as given).
 
+``PanelLasso.glm_model`` / ``glm_dual`` are the piece between two inner solves of an IRLS loop for the L1-penalised
+logistic regression (glmnet's ``family = "binomial"``), and ``logistic_path`` / ``logistic_cv`` the drivers on top: the
+inner solves are the weighted lasso above, unchanged.
+
 All compute goes through libbpgl.so (bpgl_panel_* in include/bpgl.h).
 """
 import contextlib
@@ -90,6 +94,10 @@ _PANEL_SIGS = {
     "bpgl_panel_set_positive": (ctypes.c_int, [_p, ctypes.c_int]),
     "bpgl_panel_set_penalty": (ctypes.c_int, [_p, _p]),
     "bpgl_panel_set_row_weights": (ctypes.c_int, [_p, _p, _p]),
+    "bpgl_panel_glm_model": (ctypes.c_int, [_p, ctypes.c_int, _p, _p, _p, _p, _p, _p, _p, _p,
+                                            ctypes.POINTER(ctypes.c_double)]),
+    "bpgl_panel_glm_dual": (ctypes.c_int, [_p, _p, _p, _p, ctypes.POINTER(ctypes.c_double),
+                                           ctypes.POINTER(ctypes.c_double)]),
 }
 N._SIGS.update(_PANEL_SIGS)
 
@@ -327,6 +335,61 @@ class PanelLasso:
             N.check(_lib().bpgl_panel_set_row_weights(self._ctx, N.ptr(self._wt), N.ptr(self._hd)),
                     "bpgl_panel_set_row_weights")
         self.stream.synchronize()
+
+    def set_row_weights_device(self, W, H=None):
+        """``set_row_weights`` with device fp64 tensors [k][m] (``H`` None: the row mask's rule) straight to
+        bpgl_panel_set_row_weights, which validates them on the device: no host round trip."""
+        for t in (W, H):
+            if t is not None and not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+                                      and tuple(t.shape) == (self.nrhs, self.MAT_HEIGHT)):
+                raise ValueError(f"device weights must be contiguous fp64 [k][m] = [{self.nrhs}][{self.MAT_HEIGHT}]")
+        with self._on_stream():
+            self._wt, self._hd = W, H
+            N.check(_lib().bpgl_panel_set_row_weights(self._ctx, N.ptr(W), N.ptr(H)), "bpgl_panel_set_row_weights")
+        self.stream.synchronize()
+
+    GLM_KEYS = ("loss", "hold_loss", "hold_miss", "sum_omega", "l1", "phi", "steps", "flag")
+
+    def glm_model(self, Y, omega, holdout=None, curvature=None, beta0=None):
+        """One outer step of the logistic IRLS at the stored x (bpgl_panel_glm_model; one feature block, after a
+        ``solver_reset``): ``Y``, ``omega`` device fp64 [k][m] (labels in [0, 1], prior weights in [0, 1]), ``holdout``
+        the scoring weights h >= 0 or None, ``curvature`` a device int32 [k] tensor (1: Boehning's 1/4) or None,
+        ``beta0`` a device fp64 [k] tensor -- the Newton start, overwritten with the root; None uses the one of the last
+        call (zeros at first).  The intercept is the context's own switch (``set_intercept``).  Returns a dict of (k,)
+        numpy arrays loss = sum om l, hold_loss = sum h l, hold_miss = sum h [(p > 1/2) != (y > 1/2)], sum_omega,
+        l1 = sum p_j |x_j|, phi = the final |phi|, steps, flag (1: no finite intercept), and the device tensors W, Z, P
+        [k][m], beta0 [k] and AX [k][m] (buffers the next call overwrites).  Read-only for the solve and bitwise
+        repeatable."""
+        k, m = self.nrhs, self.MAT_HEIGHT
+        if getattr(self, "_glm_W", None) is None:
+            self._glm_W, self._glm_Z, self._glm_P = (torch.empty((k, m), dtype=torch.float64, device=self.device)
+                                                     for _ in range(3))
+            self._glm_b0 = torch.zeros(k, dtype=torch.float64, device=self.device)
+            self._glm_out = (ctypes.c_double * (8 * k))()
+        if beta0 is not None:
+            self._glm_b0 = beta0
+        self._glm_Y, self._glm_Om = Y, omega
+        with self._on_stream():
+            N.check(_lib().bpgl_panel_glm_model(self._ctx, 1, N.ptr(Y), N.ptr(omega), N.ptr(holdout), N.ptr(curvature),
+                                                N.ptr(self._glm_b0), N.ptr(self._glm_W), N.ptr(self._glm_Z),
+                                                N.ptr(self._glm_P), self._glm_out), "bpgl_panel_glm_model")
+        out = np.array(self._glm_out, dtype=np.float64).reshape(k, 8)
+        res = {key: out[:, i].copy() for i, key in enumerate(self.GLM_KEYS)}
+        off = self.stat("glm_ax_offset") + (self._scratch.data_ptr() + 255) // 256 * 256 - self._scratch.data_ptr()
+        res.update(W=self._glm_W, Z=self._glm_Z, P=self._glm_P, beta0=self._glm_b0,
+                   AX=self._scratch[off // 8: off // 8 + k * m].view(k, m))
+        return res
+
+    def glm_dual(self, scale):
+        """(k,) D = -sum om Nh(s p + (1 - s) y) of the last ``glm_model``'s p, labels and weights at the dual scaling
+        ``scale`` (k,) -- ``duality_gap()['scale']`` right after the inner reset (bpgl_panel_glm_dual)."""
+        k = self.nrhs
+        sc = (ctypes.c_double * k)(*np.broadcast_to(np.asarray(scale, dtype=np.float64), (k,)))
+        out = (ctypes.c_double * k)()
+        with self._on_stream():
+            N.check(_lib().bpgl_panel_glm_dual(self._ctx, N.ptr(self._glm_P), N.ptr(self._glm_Y), N.ptr(self._glm_Om),
+                                               sc, out), "bpgl_panel_glm_dual")
+        return np.array(out, dtype=np.float64)
 
     def solver_step(self, n_iter):
         with self._on_stream():
@@ -895,4 +958,270 @@ def lasso_cv(A, b, n_folds=8, mus=None, n_mus=16, hi=0.9, lo=0.1, Block=1, GAP_B
                    refit_compactions=rrun["compactions"])
         if fit_intercept:
             out["intercept"] = rrun["cert"]["intercept"][:n_mus]
+    return out
+
+
+# ---------------------------------------------------------------------------
+# Logistic lasso: IRLS on the weighted panel.  The outer step is PanelLasso.glm_model, the inner
+# solve the weighted lasso of section 16 on the working weights and response, the stopping rule the logistic
+# certificate (PanelLasso.glm_dual at the inner certificate's scale).
+# ---------------------------------------------------------------------------
+# defaults of the drivers: `inner_iters` iterations between two outer steps, the inner reset with graph capture
+LOGISTIC_INNER_ITERS = 64
+LOGISTIC_USE_GRAPH = True
+LOGISTIC_OUTER_MAX = 256
+
+
+def _check_labels(y, m):
+    """``y`` as an fp64 vector (m,), every entry in [0, 1] (ValueError otherwise).  Needs no GPU."""
+    yv = np.array(y.detach().cpu().numpy() if isinstance(y, torch.Tensor) else y, dtype=np.float64).reshape(-1)
+    if yv.size != int(m):
+        raise ValueError(f"y must have m = {int(m)} entries, got {yv.size}")
+    if not np.all(np.isfinite(yv) & (yv >= 0.0) & (yv <= 1.0)):
+        raise ValueError("every label must lie in [0, 1]")
+    return yv
+
+
+def _check_two_classes(w, yv, what):
+    """ValueError when the weighted labels of ``w`` (n_sets, m) are all one class in a set: sum w y = 0 or = sum w, so
+    the intercept has no finite root (and without it nothing can be learnt from that set)."""
+    sy, sw = w @ yv, w.sum(axis=1)
+    bad = np.flatnonzero(~((sy > 0.0) & (sy < sw)))
+    if bad.size:
+        raise ValueError(f"{what} {int(bad[0])}: the weighted labels are all one class (sum w y = {sy[bad[0]]:g}, "
+                         f"sum w = {sw[bad[0]]:g})")
+
+
+def _logistic_setup(A, y, Block, penalty_factors, sample_weight):
+    """The drivers' host-side checks, before any device work: (penalty, labels, omega or ones)."""
+    m, n = int(A.shape[0]), int(A.shape[1])
+    if int(Block) != 1:
+        raise ValueError("the logistic drivers need Block = 1")
+    penalty = _check_penalty(penalty_factors, n)
+    yv = _check_labels(y, m)
+    omega = _check_sample_weight(sample_weight, m, 1)
+    return penalty, yv, np.ones(m) if omega is None else omega
+
+
+def _logistic_context(A, k, device, fit_intercept, positive, penalty):
+    pl = PanelLasso(A, 1, nrhs=k, device=device)
+    if fit_intercept:
+        pl.set_intercept(True)
+    if positive:
+        pl.set_positive(True)
+    if penalty is not None:
+        pl.set_penalty_factors(penalty)
+    return pl
+
+
+def _rows_device(pl, v):
+    """(k, m) numpy -> contiguous device fp64 [k][m]."""
+    return torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)).to(pl.device)
+
+
+def _logistic_mu_max(pl, Yd, Omd):
+    """mu_max of column 0, read off the x = 0 model: right after the inner reset the certificate's g is 4 A^T (om o (p -
+    y)), so gnorm_inf / 4 is max_j |a_j . (om o (p - y))| / p_j (one-sided with ``positive``)."""
+    pl.set_row_weights(None)
+    pl.solver_reset(np.zeros((pl.MAT_HEIGHT, pl.nrhs)), 1.0, use_graph=False)
+    mod = pl.glm_model(Yd, Omd)
+    pl.set_row_weights_device(mod["W"])
+    pl.solver_reset(mod["Z"].t(), 1.0, use_graph=False, x0=pl.solver_x_device())
+    return float(pl.duality_gap(screen=False)["gnorm_inf"][0]) / 4.0
+
+
+def _logistic_loop(pl, Yd, Omd, Hdd, mu, target, OUTER_MAX, inner_iters, use_graph, x0=None):
+    """The IRLS loop on ``pl`` (intercept, sign constraint and factors installed): from x = 0 (or ``x0`` (n, k)) an outer
+    step -- ``glm_model`` at the stored x; P = loss + mu l1, and a column whose P rose gets curvature 1 from then on (the
+    model is formed again); the working weights installed from the device; the inner reset at B = Z, 4 mu and the stored x,
+    no copy; the inner certificate, whose scale gives ``glm_dual``; gap = P - D -- then ``inner_iters`` iterations, until
+    every column has gap <= target or OUTER_MAX outer steps have run.  ``mu``, ``target``: (k,), in the library's scale.
+    Returns dict(x (n, k), intercept, model (the last outer step's scalars), primal, dual, gap, scale, reached, first,
+    outer_iters, iters, curvature)."""
+    k, m = pl.nrhs, pl.MAT_HEIGHT
+    mu = np.broadcast_to(np.asarray(mu, dtype=np.float64), (k,)).copy()
+    curv_h = np.zeros(k, dtype=np.int32)
+    curv = torch.zeros(k, dtype=torch.int32, device=pl.device)
+    beta0 = torch.zeros(k, dtype=torch.float64, device=pl.device)
+    pl.set_row_weights(None)
+    pl.solver_reset(np.zeros((m, k)), mu, use_graph=False, x0=x0)
+    first = np.full(k, -1, dtype=np.int64)
+    P_prev, outer, iters = None, 0, 0
+    while True:
+        mod = pl.glm_model(Yd, Omd, Hdd, curv, beta0)
+        if mod["flag"].any():
+            raise ValueError(f"column {int(np.flatnonzero(mod['flag'])[0])}: the weighted labels are all one class")
+        P = mod["loss"] + mu * mod["l1"]
+        rose = np.zeros(k, dtype=bool) if P_prev is None else (P > P_prev) & (curv_h == 0)
+        if rose.any():   # Boehning's bound from here on: every decrease of the model is a decrease of P
+            curv_h[rose] = 1
+            curv.copy_(torch.from_numpy(curv_h))
+            mod = pl.glm_model(Yd, Omd, Hdd, curv, beta0)
+        P_prev = P
+        pl.set_row_weights_device(mod["W"], Hdd)
+        pl.solver_reset(mod["Z"].t(), 4.0 * mu, use_graph=use_graph, x0=pl.solver_x_device())
+        cert = pl.duality_gap(screen=False)
+        D = pl.glm_dual(cert["scale"])
+        gap = P - D
+        ok = gap <= target
+        first[ok & (first < 0)] = outer
+        if ok.all() or outer >= int(OUTER_MAX):
+            break
+        pl.solver_step(int(inner_iters))
+        iters += int(inner_iters)
+        outer += 1
+    pl.stream.synchronize()
+    return dict(x=pl.solver_x(), intercept=mod["beta0"].cpu().numpy().copy(), model=mod, primal=P, dual=D, gap=gap,
+                scale=cert["scale"], reached=ok, first=first, outer_iters=outer, iters=iters, curvature=curv_h.copy())
+
+
+def logistic_path(A, y, mus=None, n_mus=16, hi=0.9, lo=0.1, GAP_BOUND=1e-4, OUTER_MAX=LOGISTIC_OUTER_MAX,
+                  inner_iters=LOGISTIC_INNER_ITERS, fit_intercept=True, positive=False, penalty_factors=None,
+                  sample_weight=None, x0=None, Block=1, device=None, use_graph=LOGISTIC_USE_GRAPH):
+    """An L1-penalised logistic regression path as ONE panel (glmnet's ``family = "binomial"``): for every mu of a grid
+      min over x, beta0 of sum_i omega_i l(a_i . x + beta0; y_i) + mu sum_j p_j |x_j|,   l(eta; y) = log(1 + e^eta) - y eta
+    on the bf16-stored A, by IRLS on the weighted panel: every column holds the same labels, and
+    every column has its own working weights on the one bound A.
+
+    ``y``: (m,) labels in [0, 1] (ValueError outside).  ``mus``: 1 to 128 values, padded as ``lasso_path`` pads them;
+    None: mu_max = max_j |a_j . (omega o (p0 - y))| / p_j, read off the x = 0 model, then ``mu_grid(mu_max, n_mus, hi,
+    lo)``.  ``fit_intercept`` (default on, as glmnet and scikit-learn have it): beta0 is profiled out of the logistic
+    loss at every outer step.  ``positive``, ``penalty_factors``, ``sample_weight`` (omega, any scale, used as given) as
+    in ``lasso_path``.  ``x0``: (n, len(mus)) start (needs ``mus``).  ``Block`` must be 1 (ValueError otherwise).  A
+    data set whose weighted labels are all one class is refused (ValueError) before any device work.  ``shrink`` is not
+    offered: the inner screen is safe for the quadratic model only.
+
+    The loop: an outer step (the model at the stored x, the logistic certificate), then ``inner_iters`` iterations of the
+    weighted lasso on the working response; it stops when every mu has gap <= GAP_BOUND x the null deviance (sum omega l
+    at x = 0 and its own beta0: the analogue of 1/2 ||b||^2), or after OUTER_MAX outer steps.  A column whose objective
+    rose between two outer steps runs with Boehning's curvature bound from then on and is monotone from there.
+
+    Returns a dict: x (n, len(mus)), intercept, mus, mu_max (None when mus was given), deviance (sum omega l at the
+    returned point), null_deviance, primal, dual, gap, reached, outer_iters (the outer step at which that mu first met the
+    bound, else -1), iters (inner iterations run), curvature (1 where the column fell back)."""
+    penalty, yv, omega = _logistic_setup(A, y, Block, penalty_factors, sample_weight)
+    _check_two_classes(omega[None, :], yv, "data set")
+    if x0 is not None and mus is None:
+        raise ValueError("x0 needs mus: the grid the columns of x0 belong to")
+    if int(inner_iters) <= 0:
+        raise ValueError("inner_iters must be > 0")
+    if x0 is not None:
+        x0 = np.asarray(x0.detach().cpu() if isinstance(x0, torch.Tensor) else x0, dtype=np.float64)
+        want = (int(A.shape[1]), int(np.asarray(mus).size))
+        if x0.shape != want:
+            raise ValueError(f"x0 must be (n, len(mus)) = {want}, got {x0.shape}")
+    if mus is None:
+        if not 1 <= int(n_mus) <= PANEL_NRHS[-1]:
+            raise ValueError(f"logistic_path takes 1 to {PANEL_NRHS[-1]} values of mu (got {n_mus})")
+        grid, n_given = None, int(n_mus)
+        k = next(v for v in PANEL_NRHS if v >= n_given)
+    else:
+        grid, n_given = pad_mus(mus)
+        k = grid.size
+    from .cpu_calculation import logistic_null_deviance
+    pl = _logistic_context(A, k, device, fit_intercept, positive, penalty)
+    cw = float(omega.max())
+    Yd = _rows_device(pl, np.repeat(yv[None, :], k, axis=0))
+    Omd = _rows_device(pl, np.repeat((omega / cw)[None, :], k, axis=0))
+    null = logistic_null_deviance(yv, omega, bool(fit_intercept))
+    mu_max = None
+    if grid is None:
+        mu_max = cw * _logistic_mu_max(pl, Yd, Omd)
+        grid, _ = pad_mus(_grid_below(mu_max, n_given, hi, lo, positive))
+    if x0 is not None:
+        x0 = np.concatenate([x0, np.repeat(x0[:, [int(np.argmax(grid[:n_given]))]], k - n_given, axis=1)], axis=1)
+    run = _logistic_loop(pl, Yd, Omd, None, grid / cw, float(GAP_BOUND) * null / cw, OUTER_MAX, inner_iters, use_graph,
+                         x0=x0)
+    g = slice(0, n_given)
+    return dict(x=run["x"][:, g], intercept=run["intercept"][g], mus=grid[g].copy(), mu_max=mu_max,
+                deviance=run["model"]["loss"][g] * cw, null_deviance=null, primal=run["primal"][g] * cw,
+                dual=run["dual"][g] * cw, gap=run["gap"][g] * cw, reached=run["reached"][g],
+                outer_iters=run["first"][g], iters=run["iters"], curvature=run["curvature"][g])
+
+
+def logistic_cv(A, y, n_folds=8, mus=None, n_mus=16, hi=0.9, lo=0.1, GAP_BOUND=1e-4, OUTER_MAX=LOGISTIC_OUTER_MAX,
+                inner_iters=LOGISTIC_INNER_ITERS, seed=0, masks=None, fit_intercept=True, positive=False,
+                penalty_factors=None, sample_weight=None, refit=True, return_x=False, Block=1, device=None,
+                use_graph=LOGISTIC_USE_GRAPH):
+    """K-fold cross-validation of the L1-penalised logistic regression over a grid of mu as ONE panel, with
+    ``lasso_cv``'s layout and padding: column c = f * n_mus + j solves fold f at ``mus[j]`` with the prior weights
+    fold_f o omega and is scored on the held-out rows with the weights h = (1 - fold_f) o omega.  K folds x J values of mu
+    have K J different sets of working weights on one bound A.
+
+    Arguments as ``logistic_path`` and ``lasso_cv`` (``masks``: (n_folds, m) 0/1, 0 = held out).  One grid serves all
+    folds; with ``mus=None`` mu_max is that of the full data.  ValueError before any device work for labels outside
+    [0, 1], ``Block`` != 1, and a fold (or the full data) whose weighted training labels are all one class.
+
+    Returns a dict: mus; deviance (n_folds, n_mus) = 2 sum h l / sum h and error (n_folds, n_mus) = the weighted
+    misclassification rate sum h [(p > 1/2) != (y > 1/2)] / sum h of the held-out rows; for each of the two scores s:
+    mean_s, se_s, best_s, best_1se_s (``lasso_cv``'s rules); best / best_1se (those of the deviance); reached, gap,
+    outer_iters, curvature (n_folds, n_mus); intercept_folds; iters; masks.  ``return_x``: x_folds (n, n_folds, n_mus).
+    ``refit``: the full-data path on the grid on the SAME context: x (n, n_mus), intercept, refit_gap, refit_reached."""
+    from .cpu_calculation import kfold_masks, logistic_null_deviance
+    penalty, yv, omega = _logistic_setup(A, y, Block, penalty_factors, sample_weight)
+    m = yv.size
+    if masks is not None:
+        masks = (np.asarray(masks.detach().cpu() if isinstance(masks, torch.Tensor) else masks) != 0).astype(np.uint8)
+        if masks.ndim != 2 or masks.shape[1] != m:
+            raise ValueError(f"masks must be (n_folds, m = {m})")
+        n_folds = masks.shape[0]
+    n_folds = int(n_folds)
+    if n_folds < 2:
+        raise ValueError(f"logistic_cv needs n_folds >= 2 (got {n_folds})")
+    if mus is not None:
+        mus = np.asarray(mus, dtype=np.float64).reshape(-1).copy()
+        n_mus = mus.size
+    n_mus = int(n_mus)
+    ncol = n_folds * n_mus
+    if n_mus < 1 or ncol > PANEL_NRHS[-1]:
+        raise ValueError(f"logistic_cv takes n_folds * n_mus between 2 and {PANEL_NRHS[-1]} (got {n_folds} x {n_mus})")
+    if int(inner_iters) <= 0:
+        raise ValueError("inner_iters must be > 0")
+    if masks is None:
+        masks = kfold_masks(m, n_folds, seed)
+    wf = masks.astype(np.float64) * omega                     # (n_folds, m): the fold's prior weights
+    hf = (1.0 - masks.astype(np.float64)) * omega             # ... and its scoring weights
+    _check_two_classes(omega[None, :], yv, "data set")
+    _check_two_classes(wf, yv, "fold")
+    if not np.all(hf.sum(axis=1) > 0.0):
+        raise ValueError("a fold has no held-out row of positive weight")
+    fit_intercept = bool(fit_intercept)
+    k = next(v for v in PANEL_NRHS if v >= ncol)
+    pl = _logistic_context(A, k, device, fit_intercept, positive, penalty)
+    cw = float(omega.max())
+    if mus is None:
+        mu_max = cw * _logistic_mu_max(pl, _rows_device(pl, np.repeat(yv[None, :], k, axis=0)),
+                                       _rows_device(pl, np.repeat((omega / cw)[None, :], k, axis=0)))
+        mus = _grid_below(mu_max, n_mus, hi, lo, positive)
+    cols = np.concatenate([np.arange(ncol), np.zeros(k - ncol, dtype=np.int64)])   # the pad: copies of column 0
+    fold, jmu = cols // n_mus, cols % n_mus
+    Yd = _rows_device(pl, np.repeat(yv[None, :], k, axis=0))
+    null = np.array([logistic_null_deviance(yv, wf[f], fit_intercept) for f in range(n_folds)])
+    run = _logistic_loop(pl, Yd, _rows_device(pl, (wf / cw)[fold]), _rows_device(pl, hf[fold]), mus[jmu] / cw,
+                         float(GAP_BOUND) * null[fold] / cw, OUTER_MAX, inner_iters, use_graph)
+    shape = (n_folds, n_mus)
+    hsum = hf.sum(axis=1)[:, None]
+    scores = dict(deviance=2.0 * run["model"]["hold_loss"][:ncol].reshape(shape) / hsum,
+                  error=run["model"]["hold_miss"][:ncol].reshape(shape) / hsum)
+    out = dict(mus=mus.copy(), iters=run["iters"], reached=run["reached"][:ncol].reshape(shape),
+               gap=run["gap"][:ncol].reshape(shape) * cw, outer_iters=run["first"][:ncol].reshape(shape),
+               curvature=run["curvature"][:ncol].reshape(shape),
+               intercept_folds=run["intercept"][:ncol].reshape(shape), masks=masks)
+    for name, sc in scores.items():
+        mean = sc.mean(axis=0)
+        se = sc.std(axis=0, ddof=1) / np.sqrt(n_folds)
+        best = int(np.argmin(mean))
+        within = np.flatnonzero(mean <= mean[best] + se[best])
+        out.update({name: sc, "mean_" + name: mean, "se_" + name: se, "best_" + name: best,
+                    "best_1se_" + name: int(within[np.argmax(mus[within])])})
+    out.update(best=out["best_deviance"], best_1se=out["best_1se_deviance"])
+    if return_x:
+        out["x_folds"] = run["x"][:, :ncol].reshape(-1, n_folds, n_mus)
+    if refit:
+        grid = np.concatenate([mus, np.full(k - n_mus, mus.max())])   # pad_mus' layout at this panel's width
+        rnull = logistic_null_deviance(yv, omega, fit_intercept)
+        rrun = _logistic_loop(pl, Yd, _rows_device(pl, np.repeat((omega / cw)[None, :], k, axis=0)), None, grid / cw,
+                              float(GAP_BOUND) * rnull / cw, OUTER_MAX, inner_iters, use_graph)
+        out.update(x=rrun["x"][:, :n_mus], intercept=rrun["intercept"][:n_mus], refit_gap=rrun["gap"][:n_mus] * cw,
+                   refit_reached=rrun["reached"][:n_mus], refit_iters=rrun["iters"])
     return out

@@ -108,7 +108,13 @@ const char* bpgl_last_error(void);
  *                and the panel tuning key "row_weights" (bpgl_panel_get_tuning only).  Opt-in: with it off every
  *                kernel that existed is unchanged, bit for bit, and 0/1 weights compute what the row mask
  *                computes.  bpgl_panel_scratch_bytes grows by the weights' pieces, laid out after everything that
- *                existed (24 nrhs m + 256 bytes). */
+ *                existed (24 nrhs m + 256 bytes).
+ *   311 (0.3.11): + bpgl_panel_glm_model and bpgl_panel_glm_dual (the logistic lasso by IRLS on the weighted panel:
+ *                the piece between two inner solves -- A x in fp64, the intercept's Newton iteration, the working
+ *                weights and response, the loss scalars -- and the dual sum of the logistic certificate; DESIGN.md
+ *                section 18) and the panel stat "glm_ax_offset".  No iteration kernel has a new variant and no
+ *                existing kernel's arguments move.  bpgl_panel_scratch_bytes grows by the model's pieces, laid out
+ *                after everything that existed (about 8 nrhs m bytes). */
 int bpgl_version(void);
 
 /*
@@ -680,6 +686,47 @@ int bpgl_panel_reset_x0(bpgl_panel* ctx, const double* B, const double* mu, cons
  */
 int bpgl_panel_gather_columns(bpgl_panel* ctx, const int32_t* cols, int64_t n_out, void* A_out,
                               int64_t lda_out);
+
+/*
+ * The logistic lasso by IRLS on the weighted panel (since ABI 311).  Right-hand side k, with
+ * labels y_ki in [0, 1] and prior weights om_ki in [0, 1], solves
+ *   min over x, beta0 of sum_i om_i l(eta_i; y_i) + mu sum_j p_j |x_j|,  eta = A x + beta0,  l = log(1 + e^eta) - y eta
+ * (x >= 0, the factors p and the intercept as the context has them installed; beta0 = 0 without the intercept).  The
+ * inner solves are the weighted lasso as it stands; these two calls are what runs between them.
+ *
+ * bpgl_panel_glm_model, one outer step at the STORED x (fp32; everything below is fp64 on it and on the bf16 A
+ * widened exactly):
+ *   AX     = A x: bpgl_panel_gap's product 1 (the same kernel, chunking and launch), its chunk partials folded in
+ *            chunk order, nothing subtracted
+ *   beta0  with the intercept: the root of phi(beta) = sum_i om_i (sigma(AX_i + beta) - y_i) per right-hand side, by
+ *            a Newton iteration started at beta0[k] and safeguarded by a bracket (a step that leaves it becomes the
+ *            midpoint), at most 40 steps, stopped at |phi| <= 1e-14 sum om; written back to beta0[k].  A right-hand
+ *            side with sum om y = 0 or = sum om has no finite root: its flag is set and beta0[k] is left as it was.
+ *   P = sigma(eta);  v = max(P (1 - P), 1e-5) where curv[k] == 0, 1/4 where curv[k] != 0 (Boehning's bound: the
+ *            quadratic model then majorises the loss);  W = 4 om v in [0, 1];  Z = eta + (y - P) / v
+ *   out[8 k + 0..7] = sum om l, sum h l, sum h [(P > 1/2) != (y > 1/2)], sum om, sum_j p_j |x_j|, the final |phi|,
+ *            the Newton steps taken, the flag (1: no finite root)
+ * family: BPGL_GLM_BINOMIAL, the only one (BPGL_E_ARG otherwise).  Y, Om, W, Z, P: device fp64 [nrhs][m]; Hd: device
+ * fp64 [nrhs][m], the scoring weights h >= 0, or NULL (both scoring sums are then 0); curv: device int32 [nrhs] or
+ * NULL (all 0); beta0: device fp64 [nrhs], in / out; out: host, 8 nrhs doubles.  A null or misaligned pointer is
+ * BPGL_E_ARG before any HIP call.  Needs a bpgl_panel_reset (or _reset_x0) since bpgl_panel_bind and one feature block
+ * (BPGL_E_STATE otherwise).  Waits for the stream, as bpgl_panel_gap does.  Reads X and A only, so the solve may go on
+ * after it without a reset, and two calls on the same state return the same bits (fixed-order sums, no atomics).
+ *
+ * The caller then installs W (and h) with bpgl_panel_set_row_weights and calls bpgl_panel_reset_x0 with B = Z,
+ * 4 mu and X0 = bpgl_panel_x: the inner problem 1/2 sum W (a . x + beta0 - Z)^2 + 4 mu sum p |x| is 4 times the
+ * quadratic model of the loss at x.  Right after that reset bpgl_panel_residual is 4 om o (P - y), so bpgl_panel_gap's
+ * G is the logistic gradient (times 4) and its scale s = min(1, 4 mu / max_j |g_j| / p_j) the dual scaling.
+ *
+ * bpgl_panel_glm_dual: out[k] = D_k = -sum_i om_i Nh(s_k P_i + (1 - s_k) y_i), Nh(t) = t log t + (1 - t) log(1 - t)
+ * with 0 log 0 = 0 -- the dual value at theta = s om o (P - y), so that sum om l + mu sum p |x| - D_k bounds the
+ * suboptimality.  P, Y, Om: device fp64 [nrhs][m]; scale, out: host, nrhs doubles.  Fixed-order sums; waits.
+ */
+#define BPGL_GLM_BINOMIAL 1
+int bpgl_panel_glm_model(bpgl_panel* ctx, int family, const double* Y, const double* Om, const double* Hd,
+                         const int32_t* curv, double* beta0, double* W, double* Z, double* P, double* out);
+int bpgl_panel_glm_dual(bpgl_panel* ctx, const double* P, const double* Y, const double* Om, const double* scale,
+                        double* out);
 
 #ifdef __cplusplus
 }

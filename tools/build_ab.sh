@@ -13,9 +13,10 @@ else
 fi
 mkdir -p $R/build_ab
 # the library's translation units: the Makefile's; a ref from before ABI 308 has no bpgl_panel_pos.hip, one from
-# before ABI 309 no bpgl_panel_pen.hip / bpgl_panel_penpos.hip, one from before ABI 310 no bpgl_panel_wt.hip
+# before ABI 309 no bpgl_panel_pen.hip / bpgl_panel_penpos.hip, one from before ABI 310 no bpgl_panel_wt.hip,
+# one from before ABI 311 no bpgl_panel_glm.hip
 UNITS="$SRC/convex_optimization_amd/csrc/bpgl.hip $SRC/convex_optimization_amd/csrc/bpgl_panel_abi.hip"
-for u in bpgl_panel_pos bpgl_panel_pen bpgl_panel_penpos bpgl_panel_wt; do
+for u in bpgl_panel_pos bpgl_panel_pen bpgl_panel_penpos bpgl_panel_wt bpgl_panel_glm; do
   [ -f $SRC/convex_optimization_amd/csrc/$u.hip ] && UNITS="$UNITS $SRC/convex_optimization_amd/csrc/$u.hip"
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared "$@" -I$SRC/include $UNITS \

@@ -7,4 +7,5 @@ mkdir -p $R/build_diag
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -DBPGL_STAMP=1 -I$R/include \
     $R/convex_optimization_amd/csrc/bpgl.hip $R/convex_optimization_amd/csrc/bpgl_panel_abi.hip \
     $R/convex_optimization_amd/csrc/bpgl_panel_pos.hip $R/convex_optimization_amd/csrc/bpgl_panel_pen.hip \
-    $R/convex_optimization_amd/csrc/bpgl_panel_penpos.hip $R/convex_optimization_amd/csrc/bpgl_panel_wt.hip -o $R/build_diag/libbpgl_stamp.so -lrccl
+    $R/convex_optimization_amd/csrc/bpgl_panel_penpos.hip $R/convex_optimization_amd/csrc/bpgl_panel_wt.hip \
+    $R/convex_optimization_amd/csrc/bpgl_panel_glm.hip -o $R/build_diag/libbpgl_stamp.so -lrccl
