@@ -175,31 +175,12 @@ def test_plain_lasso_is_bitwise_the_same_after_the_glm_calls(state):
 # ---------------------------------------------------------------------------
 # 4. paths
 # ---------------------------------------------------------------------------
-GAP_BOUND, OUTER_MAX = 1e-4, 32    # the fp32-rounded numpy model of the loop needs at most 3 outer steps of 64 iterations
-                                   # on this grid (tests/test_panel_logistic_host.py runs it); 32 leaves the bf16
-                                   # direction of the device's iteration a tenfold margin
+GAP_BOUND, OUTER_MAX, check_path = I.GAP_BOUND, I.OUTER_MAX, I.check_path    # shared with the edge tests
 
 
 @pytest.fixture(scope="module")
 def path_instance():
-    return I.instance(256, 512, 1, 10, 30)
-
-
-def check_path(A, y, om, out, **kw):
-    null = out["null_deviance"]
-    assert abs(null - C.logistic_null_deviance(y, om, kw.get("intercept", True))) <= 1e-12 * null
-    assert out["reached"].all(), (out["gap"] / null, out["outer_iters"])
-    assert (out["gap"] <= GAP_BOUND * null).all() and (out["outer_iters"] >= 0).all()
-    assert np.all(np.diff(out["mus"]) < 0) and abs(out["mus"][0] / out["mu_max"] - 0.9) < 1e-12 \
-        and abs(out["mus"][-1] / out["mu_max"] - 0.3) < 1e-12
-    assert np.count_nonzero(out["x"][:, -1]) > 0
-    for j, mu in enumerate(out["mus"]):
-        ref = C.logistic_panel_solve(A, y, om, mu, outer_max=300, inner_iters=16, tol=1e-8, **kw)
-        assert ref["reached"]
-        P = I.objective(A, y, om, out["x"][:, j], out["intercept"][j], mu, kw.get("p"))
-        assert abs(P - out["primal"][j]) <= 1e-9 * P
-        # P* <= P <= P* + gap, and P* lies within the reference's own gap below P_ref
-        assert ref["primal"] - 1e-8 * null <= P <= ref["primal"] + GAP_BOUND * null, (j, P, ref["primal"])
+    return I.path_instance()
 
 
 def test_logistic_path(path_instance):

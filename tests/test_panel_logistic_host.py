@@ -8,6 +8,14 @@
     Boehning's bound the objective is monotone.
 (3) two mutants of the certificate, each caught by a negative gap.
 (4) the drivers' ValueErrors, raised before any device work.
+(5) the edge instances of tests/test_panel_logistic_edges.py reach the branches they are built for (the floor, p = 1
+    exactly, the midpoint fallback, a start outside the bracket, the one-class flag), the copies of the Newton loop and
+    of the model in the instance module return what the originals return, and the restatement passes the edge
+    assertions against itself and against a bisection in long double.
+(6) five mutants of the restatement, each rejected by the assertions the GPU tests run: the floor removed (W and Z on the
+    floor rows), the bracket over all rows (the step count alone), the fallback to ``lo`` (the step count in every
+    two-cluster column; the root itself where 40 steps no longer reach it), ``>=`` in the miss rule (hold_miss of the
+    fractional labels), 0 log 0 guarded on one side only (the dual at s = 1 where p = 1, and at s = 0: NaN).
 
 Bounds.  Weak duality is exact in exact arithmetic; -1e-12 P allows the fp64 rounding of sums of m <= 256 terms of
 size <= P.  The KKT bound is not a free tolerance: the gradient mapping G_L of an L-smooth loss plus a prox-friendly
@@ -245,3 +253,164 @@ def test_driver_value_errors():
         panel.logistic_cv(A, y, masks=masks, n_mus=4)
     with pytest.raises(ValueError):
         C.logistic_model(np.zeros((4, 2)), [0, 1, 2, 0], np.ones(4), np.zeros(2))
+
+
+# ---------------------------------------------------------------------------
+# (5) the edge instances of tests/test_panel_logistic_edges.py are what they claim to be
+# ---------------------------------------------------------------------------
+EDGE_SHAPES = {"256x512x16": (256, 512, 16), "768x256x32": (768, 256, 32), "256x512x64": (256, 512, 64),
+               "4096x256x16": (4096, 256, 16)}
+_edges = {}
+
+
+def edge_state(shape):
+    """the instance, per column the restatement, the Newton loop's trace, the exact-count class and the long double
+    root; computed once per shape"""
+    if shape not in _edges:
+        inst = I.edge_instance(*EDGE_SHAPES[shape])
+        A, Y, Om, H, X, B0 = (inst[q] for q in ("A", "Y", "Om", "H", "X", "B0"))
+        k = inst["k"]
+        ref = [C.logistic_model(A, Y[c], Om[c], X[:, c], B0[c], True, 0, H[c]) for c in range(k)]
+        _edges[shape] = dict(
+            inst=inst, ref=ref, trace=[I.newton_trace(ref[c]["ax"], Y[c], Om[c], B0[c]) for c in range(k)],
+            stable=[bool(ref[c]["flag"]) or I.count_is_stable(ref[c]["ax"], Y[c], Om[c], B0[c]) for c in range(k)],
+            root=[None if ref[c]["flag"] else I.root_longdouble(ref[c]["ax"], Y[c], Om[c]) for c in range(k)])
+    return _edges[shape]
+
+
+@pytest.mark.parametrize("shape", list(EDGE_SHAPES))
+def test_edge_instances_reach_the_branches(shape):
+    e = edge_state(shape)
+    inst, ref, trace = e["inst"], e["ref"], e["trace"]
+    A, Y, Om, X, B0, k = inst["A"], inst["Y"], inst["Om"], inst["X"], inst["B0"], inst["k"]
+    assert (I.bf16(A) == A).all() and (X.astype(np.float32).astype(np.float64) == X).all()
+    floor = np.array([np.mean(r["v"] == C.GLM_FLOOR) for r in ref])
+    # the floor: a mixed share on every saturated column scaled by 8 or by 40, none at scale 1; and p rounded to
+    # exactly 1 on rows with a weight
+    sat = I.columns_of(inst, "sat")
+    assert sorted({inst["kinds"][c]["scale"] for c in sat}) == [1.0, 8.0, 40.0] and len(sat) == 3 * (k // 16)
+    assert all((floor[c] > 0) == (inst["kinds"][c]["scale"] != 1.0) for c in sat), floor[sat]
+    assert all(floor[c] < 1 for c in sat)
+    assert any(((ref[c]["p"] == 1.0) & (Om[c] > 0)).any() for c in I.columns_of(inst, "sat"))
+    # the safeguards: every two-cluster column falls back to the midpoint, the far start lies outside the bracket,
+    # and the zero-weight rows lie outside the weighted rows' range, so a bracket over all rows is another bracket
+    two = I.columns_of(inst, "two")
+    assert len(two) == 9 * (k // 16) and sum(inst["kinds"][c]["far_start"] for c in two) >= len(two) // 2
+    for c in two:
+        t, kd = trace[c], inst["kinds"][c]
+        assert 6 <= t["steps"] <= 12 and 1 <= t["fallbacks"] <= 5, (c, kd, t)
+        assert t["outside"] == kd["far_start"] and (B0[c] == I.FAR_START) == kd["far_start"]
+        assert (Om[c, inst["far"]] == 0).all() and ref[c]["ax"][inst["far"]].min() > ref[c]["ax"][Om[c] > 0].max()
+        assert I.newton_trace(ref[c]["ax"], Y[c], Om[c], B0[c], all_rows=True)["lo"] < t["lo"] - 100.0
+        assert floor[c] > 0 and ref[c]["phi"] <= 1e-12 * Om[c].sum()
+    assert all(trace[c]["fallbacks"] == 0 and not trace[c]["outside"] for c in I.columns_of(inst, "sat", "frac"))
+    # the one-class flag, exactly there
+    assert [c for c in range(k) if ref[c]["flag"] == 1] == I.columns_of(inst, "one")
+    for c in I.columns_of(inst, "one"):
+        assert ref[c]["steps"] == 0 and ref[c]["beta0"] == B0[c] != 0.0
+    # fractional labels: the three exact values are there
+    for c in I.columns_of(inst, "frac"):
+        assert [(Y[c] == v).sum() for v in (0.5, 0.0, 1.0)] == [12, 12, 12] and floor[c] > 0
+    # the step count is a property of the instance, not of the last bit of exp, in at least 90 % of the columns
+    rooted = [c for c in range(k) if not ref[c]["flag"]]
+    assert np.mean([e["stable"][c] for c in rooted]) >= 0.9
+
+
+@pytest.mark.parametrize("shape", ["256x512x16", "768x256x32"])
+def test_the_copies_return_what_the_originals_return(shape):
+    e = edge_state(shape)
+    inst = e["inst"]
+    for c in range(inst["k"]):
+        y, om, x, b0, h = inst["Y"][c], inst["Om"][c], inst["X"][:, c], inst["B0"][c], inst["H"][c]
+        r, t = e["ref"][c], e["trace"][c]
+        assert (t["beta"], t["phi"], t["steps"], t["flag"]) == C.logistic_intercept(r["ax"], y, om, b0)
+        for icpt, want in ((True, r), (False, C.logistic_model(inst["A"], y, om, x, b0, False, 0, h))):
+            mine = I.edge_model(inst["A"], y, om, x, b0, icpt, h)
+            assert mine.keys() == want.keys()
+            for key in want:
+                assert np.asarray(mine[key]).tobytes() == np.asarray(want[key]).tobytes(), (c, icpt, key)
+        assert I.dual_one_sided(y, om, np.clip(r["p"], 1e-3, 0.999), 0.7) == \
+            C.logistic_dual(y, om, np.clip(r["p"], 1e-3, 0.999), 0.7)
+
+
+@pytest.mark.parametrize("shape", list(EDGE_SHAPES))
+def test_the_restatement_passes_its_own_edge_assertions(shape):
+    """with itself as the other side, the long double root included: the derived beta0 bound holds for the Newton root"""
+    e = edge_state(shape)
+    inst = e["inst"]
+    for c in range(inst["k"]):
+        y, om, h, r = inst["Y"][c], inst["Om"][c], inst["H"][c], e["ref"][c]
+        I.check_model_column(r, r, y, om, e["stable"][c], root=e["root"][c])
+        for sc in (1.0, 0.0, 0.5, 1e-8):
+            I.check_dual(C.logistic_dual(y, om, r["p"], sc), y, om, r["p"], sc)
+
+
+def test_bohning_reference_has_steps_that_descend():
+    """at 0.3 mu_max every column lowers P by more than 1e-6 x the null deviance in at least 4 of the 6 outer steps"""
+    want = I.bohning_reference()
+    drop = -np.diff(want["history"], axis=1)
+    assert drop.shape == (I.BOHNING_SHAPE[2], I.BOHNING_OUTER)
+    assert ((drop > 1e-6 * want["null"][:, None]).sum(axis=1) >= 4).all(), (drop / want["null"][:, None]).round(7)
+    assert (drop >= 0.0).all()
+
+
+# ---------------------------------------------------------------------------
+# (6) mutants of the restatement, each rejected by the assertions the GPU tests run (``check_model_column``, ``check_dual``)
+# ---------------------------------------------------------------------------
+def rejections(shape="256x512x16", **mutant):
+    """{assertion name: [columns]} over the columns of the shape, the mutant ``edge_model`` against the restatement"""
+    e = edge_state(shape)
+    inst, out = e["inst"], {}
+    for c in range(inst["k"]):
+        y, om, x, b0, h = inst["Y"][c], inst["Om"][c], inst["X"][:, c], inst["B0"][c], inst["H"][c]
+        failed = []
+        I.check_model_column(I.edge_model(inst["A"], y, om, x, b0, True, h, **mutant), e["ref"][c], y, om,
+                             e["stable"][c], root=e["root"][c], collect=failed)
+        for msg in failed:
+            out.setdefault(msg[0], []).append(c)
+    return inst, out
+
+
+def test_no_mutation_no_rejection():
+    assert rejections()[1] == {}
+
+
+def test_mutant_floor_removed_is_caught():
+    inst, out = rejections(floor=False)
+    floored = [c for c in range(inst["k"]) if inst["kinds"][c]["kind"] in ("sat", "two", "frac")
+               and inst["kinds"][c].get("scale") != 1.0]
+    assert set(out["W on the floor"]) >= set(I.columns_of(inst, "two")) and len(out["W on the floor"]) >= 11
+    assert set(out["Z on the floor"]) == set(out["W on the floor"]) <= set(floored)
+    assert "beta0" not in out and "steps" not in out           # nothing else moved
+
+
+def test_mutant_bracket_over_all_rows_is_caught():
+    """the root is the same root: only the step count tells"""
+    inst, out = rejections(all_rows=True)
+    assert set(out) == {"steps"} and set(out["steps"]) <= set(I.columns_of(inst, "two")) and len(out["steps"]) >= 3
+
+
+def test_mutant_fallback_to_lo_is_caught():
+    inst, out = rejections(fallback="lo")
+    assert set(out["steps"]) == set(I.columns_of(inst, "two"))
+
+
+def test_mutant_miss_rule_with_ge_is_caught():
+    inst, out = rejections(miss_ge=True)
+    assert out == {"hold_miss": I.columns_of(inst, "frac")}
+
+
+def test_mutant_one_sided_zero_log_zero_is_caught():
+    e = edge_state("256x512x16")
+    inst, caught = e["inst"], {1.0: [], 0.0: []}
+    for c in range(inst["k"]):
+        y, om, p = inst["Y"][c], inst["Om"][c], e["ref"][c]["p"]
+        for sc in caught:
+            try:
+                I.check_dual(I.dual_one_sided(y, om, p, sc), y, om, p, sc)
+            except AssertionError as err:
+                assert err.args[0][0] == "dual" and np.isnan(err.args[0][1])
+                caught[sc].append(c)
+    # s = 1: where p rounds to 1 on a row with a weight; s = 0: t = y, every column with a label 1
+    assert set(caught[1.0]) >= {c for c in I.columns_of(inst, "sat") if inst["kinds"][c]["scale"] == 40.0}
+    assert len(caught[0.0]) >= inst["k"] - 2
